@@ -19,6 +19,11 @@ all-reduce of [sum ln P, node_freq[N]] per step.  `--scaling weak
 20x read set instead.  `python bench.py --gpus N` without RANK in the environment starts the N ranks itself
 (fresh child processes, created before this process touches a GPU); under torch.distributed.run it is a rank.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  `--full` adds what takes work of its own:
+the CPU baseline with its parity check, and for the mapping step a call without grouping hints, the frontier
+profile and the hinted forward score on the step's mappings.  `--dump-outputs DIR` writes what the timed path
+computed in its last step as DIR/<name>.npy (float64; a fixed, seeded sample of the mapping lists).
 """
 from __future__ import annotations
 
@@ -132,6 +137,36 @@ def frontier_profile(rc, mp):
             "wide_frontier_reads": int(((flags & _ffi.PHMM_READ_WIDE_FRONTIER) != 0).sum()),
             "deferred_reads": int(((flags & _ffi.PHMM_READ_DEFERRED) != 0).sum()),
             "mean_dense_cols": float(cols.mean()) if cols.size else 0.0, "max_dense_cols": int(cols.max()) if cols.size else 0}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def mapping_sample(mp, n_positions: int = 1 << 15, width: int = 64):
+    """A fixed sample of a Mappings for --dump-outputs: `n_positions` read positions drawn with a fixed seed from the
+    read set alone (the same positions for every build), each with its list length and the first min(length, `width`)
+    entries of its list in the order the caller receives them, concatenated position after position (a CSR like the
+    caller's, without padding).  At most 32 MB."""
+    po, nd, lp = mp.arrays()
+    n_pos = po.shape[0] - 1
+    pick = np.sort(np.random.default_rng(7).choice(n_pos, size=min(n_positions, n_pos), replace=False))
+    lo, hi = po[pick].astype(np.int64), po[pick + 1].astype(np.int64)
+    take = np.minimum(hi - lo, width)
+    start = np.cumsum(take) - take
+    src = np.arange(int(take.sum())) + np.repeat(lo - start, take)
+    return {"mapping_positions": pick.astype(np.float64), "mapping_list_len": (hi - lo).astype(np.float64),
+            "mapping_nodes": nd[src].astype(np.float64), "mapping_logp": lp[src]}
+
+
+def dump_outputs(path: str, outputs: dict) -> None:
+    """--dump-outputs: every array as float64 path/<name>.npy, DUMP_LIMIT_BYTES at most in all."""
+    arrs = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def cpu_baseline(arrays, reads, mode: str, gpu_logp, gpu_check, budget_s: float = 20.0):
@@ -289,12 +324,19 @@ def main():
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong")
     ap.add_argument("--mode", choices=("mapping", "candidates", "map_nodes"), default="mapping")
     ap.add_argument("--candidates", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes work of its own: CPU baseline + parity, un-hinted call, "
+                         "frontier profile, hinted forward score")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
     ap.add_argument("--spin-up", type=float, default=2.0,
                     help="seconds of extra UNTIMED steps behind the warm-up (not part of --warmup or --steps): the first "
                          "GPU process on a fresh box runs its first seconds of steps 10-15 %% slower than a warm one")
     ap.add_argument("--read-len", type=int, default=0, help="override the workload's read length (e.g. 10000: HiFi)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -382,6 +424,8 @@ def main():
             mp1 = mp0.map_nodes(model1, map_off, map_nodes)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, mapping_sample(mp1))
         e0, e1 = int(mp0.arrays()[1].shape[0]), int(mp1.arrays()[1].shape[0])
         # what the carried lists are for: the hinted likelihood on the k+1 graph (to_full_prob_reads with mappings)
         tot1, lp1 = model1.to_full_prob_reads(rc, mp1)
@@ -419,7 +463,7 @@ def main():
 
     def step():
         if args.mode == "candidates":
-            tot, _ = model.to_full_prob_reads_copy_nums(rc, state["mappings"], cand, 0)
+            tot, state["candidate_read_logp"] = model.to_full_prob_reads_copy_nums(rc, state["mappings"], cand, 0)
             cand_tot.zero_()
             cand_tot[c_lo:c_hi] = torch.from_numpy(tot).to(dev)
             if dist is not None:
@@ -430,7 +474,7 @@ def main():
                 state["ar_ms"] += (time.perf_counter() - t0) * 1e3
             return
         if w["mode"] == "dense":
-            model.run_dense(rc, True, True, out_logp=out_logp, out_node_freq=red[1:])
+            _, state["read_logp_backward"], _ = model.run_dense(rc, True, True, out_logp=out_logp, out_node_freq=red[1:])
             red[0] = out_logp.sum()
         else:
             mp, _ = model.generate_mappings(rc, None, True, out_node_freq=red[1:])
@@ -516,8 +560,27 @@ def main():
     else:
         cand_work = float(args.candidates) * total_bases
 
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results (with N > 1: node_freq / candidate totals after the all-reduce, per-read
+        # values of rank 0's reads)
+        if args.mode == "candidates":
+            lp = state["candidate_read_logp"]
+            cols = np.arange(lp.shape[1])
+            if lp.nbytes > DUMP_LIMIT_BYTES // 2:
+                cols = np.sort(np.random.default_rng(7).choice(lp.shape[1], size=(DUMP_LIMIT_BYTES // 2) // (8 * lp.shape[0]),
+                                                                replace=False))
+            outs = {"candidate_logp_total": cand_tot.cpu().numpy(), "candidate_read_logp": lp[:, cols],
+                    "candidate_read_index": cols}
+        else:
+            outs = {"read_logp": out_logp.cpu().numpy(), "node_freq": red[1:].cpu().numpy()}
+            if w["mode"] == "dense":
+                outs["read_logp_backward"] = state["read_logp_backward"]
+            else:
+                outs.update(mapping_sample(state["mappings"]))
+        dump_outputs(args.dump_outputs, outs)
+
     extra = {}
-    if w["mode"] == "sparse" and rank == 0 and args.mode == "mapping":
+    if args.full and w["mode"] == "sparse" and rank == 0 and args.mode == "mapping":
         # a call without grouping hints on a warm pool: what `infer` sees at a new k (new graph, same reads)
         rc_cold = D.ReadCollection(reads)
         torch.cuda.synchronize()
@@ -581,7 +644,7 @@ def main():
                                 "kernel_ms_per_step": ms / max(args.steps, 1), "launches_per_step": n // max(args.steps, 1),
                                 "note": "latency / instruction-issue bound (one wave walks one read for one candidate); "
                                         "HBM fraction reported for the contract only"}}
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 cb, olp = cpu_baseline_candidates(arrays, reads, mp.arrays(), rc.offsets)
                 _, glp = model.to_full_prob_reads_copy_nums(rc, mp, cand[:1], 1)  # candidate 0 == the mapping model's copy numbers
                 cb["max_abs_dlogp"] = float(np.max(np.abs(glp[0][:olp.shape[0]] - olp)))
@@ -619,7 +682,7 @@ def main():
                                            "(frontiers of 65-400 nodes: instruction-issue / barrier bound, SQ counters in "
                                            "profiles/r3_rep20_sq_counters.txt); this object describes the dense warm-up's "
                                            "bwd_step launches only")
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 def gpu_check(sample):
                     return model.run_dense(D.ReadCollection(sample), False, False)[0]
                 out["cpu_baseline"] = cpu_baseline(arrays, reads, w["mode"], out_logp.cpu().numpy(), gpu_check)

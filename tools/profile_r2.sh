@@ -6,16 +6,16 @@ OUT=$PWD/gpurun_out/prof_r2
 REPO=$PWD
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cfg3_stats -o stats -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cfg3_bench_under_rocprof.json 2> $OUT/cfg3_stats.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cfg3_stats -o stats -- python3 $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cfg3_bench_under_rocprof.json 2> $OUT/cfg3_stats.err
 echo cfg3 stats done
 rocprofv3 --output-format csv --pmc FETCH_SIZE --kernel-trace -d $OUT/calib_fetch -- $REPO/tools/pmc_calib > $OUT/calib_fetch.log 2>&1
 rocprofv3 --output-format csv --pmc WRITE_SIZE --kernel-trace -d $OUT/calib_write -- $REPO/tools/pmc_calib > $OUT/calib_write.log 2>&1
 rocprofv3 --output-format csv --pmc FETCH_SIZE --kernel-trace -d $OUT/bench_fetch -- python3 $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_fetch.log 2>&1
 rocprofv3 --output-format csv --pmc WRITE_SIZE --kernel-trace -d $OUT/bench_write -- python3 $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_write.log 2>&1
 echo cfg3 pmc done
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cfg2_stats -o stats -- python3 $REPO/bench.py --workload cfg2 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cfg2_bench_under_rocprof.json 2> $OUT/cfg2_stats.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cfg2_stats -o stats -- python3 $REPO/bench.py --full --workload cfg2 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cfg2_bench_under_rocprof.json 2> $OUT/cfg2_stats.err
 echo cfg2 stats done
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cand_stats -o stats -- python3 $REPO/bench.py --mode candidates --candidates 64 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cand64_bench_under_rocprof.json 2> $OUT/cand_stats.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cand_stats -o stats -- python3 $REPO/bench.py --full --mode candidates --candidates 64 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cand64_bench_under_rocprof.json 2> $OUT/cand_stats.err
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d $OUT/cand_p1 -- python3 $REPO/bench.py --mode candidates --candidates 64 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/cand_p1.log 2>&1
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU -d $OUT/cand_p2 -- python3 $REPO/bench.py --mode candidates --candidates 64 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/cand_p2.log 2>&1
 echo candidates done

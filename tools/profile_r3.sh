@@ -8,7 +8,7 @@ REPO=$PWD
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 [ -x $REPO/tools/pmc_calib ] || /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -o $REPO/tools/pmc_calib $REPO/tools/pmc_calib.hip
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cfg3_stats -o stats -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cfg3_bench_under_rocprof.json 2> $OUT/cfg3_stats.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cfg3_stats -o stats -- python3 $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cfg3_bench_under_rocprof.json 2> $OUT/cfg3_stats.err
 echo cfg3 stats done
 if [ "$1" != "quick" ]; then
 rocprofv3 --output-format csv --pmc FETCH_SIZE --kernel-trace -d $OUT/calib_fetch -- $REPO/tools/pmc_calib > $OUT/calib_fetch.log 2>&1
@@ -21,9 +21,9 @@ rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INS
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM -d $OUT/sq_p2 -- python3 $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $OUT/sq_p2.log 2>&1
 echo cfg3 sq done
 if [ "$1" != "quick" ]; then
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cfg3_L10k_stats -o stats -- python3 $REPO/bench.py --read-len 10000 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cfg3_L10k_bench_under_rocprof.json 2> $OUT/cfg3_L10k_stats.err
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/rep_stats -o stats -- python3 $REPO/bench.py --workload rep --steps 3 --warmup 1 --no-cpu-baseline > $OUT/rep_bench_under_rocprof.json 2> $OUT/rep_stats.err
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/rep20_stats -o stats -- python3 $REPO/bench.py --workload rep20 --steps 2 --warmup 2 --no-cpu-baseline > $OUT/rep20_bench_under_rocprof.json 2> $OUT/rep20_stats.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/cfg3_L10k_stats -o stats -- python3 $REPO/bench.py --full --read-len 10000 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/cfg3_L10k_bench_under_rocprof.json 2> $OUT/cfg3_L10k_stats.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/rep_stats -o stats -- python3 $REPO/bench.py --full --workload rep --steps 3 --warmup 1 --no-cpu-baseline > $OUT/rep_bench_under_rocprof.json 2> $OUT/rep_stats.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/rep20_stats -o stats -- python3 $REPO/bench.py --full --workload rep20 --steps 2 --warmup 2 --no-cpu-baseline > $OUT/rep20_bench_under_rocprof.json 2> $OUT/rep20_stats.err
 echo long-read stats done
 fi
 cd $REPO
