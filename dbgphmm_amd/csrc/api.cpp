@@ -636,6 +636,18 @@ int phmm_mappings_read_logp(const phmm_mappings *mp, double *out_logp, double *o
     });
 }
 
+int phmm_mappings_read_logp_backward(const phmm_mappings *mp, double *out_logp, double *out_total) {
+    return guarded([&] {
+        if (!mp) PHMM_THROW(PHMM_EINVAL, "NULL mappings");
+        if (mp->read_logp_backward.size() != mp->R)
+            PHMM_THROW(PHMM_EINVAL, "these mappings were not produced by phmm_generate_mappings");
+        double tot = 0.0;
+        for (double v : mp->read_logp_backward) tot += v;
+        put_doubles(out_logp, mp->read_logp_backward.data(), mp->R);
+        put_doubles(out_total, &tot, 1);
+    });
+}
+
 // Mappings::to_node_freqs (hint.rs:161-171): freq[v] = sum of linear probs over all lists
 int phmm_mappings_node_freqs(const phmm_mappings *mp, uint32_t n_nodes, double *out) {
     return guarded([&] {

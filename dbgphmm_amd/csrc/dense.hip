@@ -497,13 +497,14 @@ __device__ __forceinline__ double dev_logadd(double x, double y) {
 
 // Begin-state chain of backward column p from the per-block partial sums of launch p
 // (bmb / bib, backward.rs:499-555), log domain.  Runs in block lb==0 of launch p-1 and
-// in bwd_finish for p == 0.
+// in bwd_finish for p == 0.  With a sparse tail (bstart) the chain starts at column bstart+1, whose InsBegin the
+// sparse backward kernel wrote: the dense head computes columns 0 .. bstart only.
 template <int W>
 __device__ __forceinline__ void bwd_chain(const DenseArgs &a, int g, int p, double *lds) {
     constexpr int ROWS = BLOCK / W;
     const int r = threadIdx.x % W, row = threadIdx.x / W;
     const int len = a.len[g * W + r];
-    const bool live = p < len;
+    const bool live = p < len && (!a.bstart || p <= (a.bstart[g * W + r] & ~(1 << 30)));
     double s1 = 0.0, s2 = 0.0;
     if (live) {
         const double *bp = a.bpart + ((size_t)(p & 1) * a.ng + g) * a.nblk8 * W * 2;

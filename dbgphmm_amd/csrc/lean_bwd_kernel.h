@@ -4,6 +4,7 @@
 //
 //   B.tables[pos] over the `na` best nodes of F.tables[pos-1]         backward.rs:122-129, table.rs:117-123
 //   b_step restricted to that list: bd0 + n_max_gaps x bdt, bm, bi    backward.rs:216-261, 299-483
+//   begin states bmb / bib of the column over the list                backward.rs:499-555
 //   S[pos-1] = F.tables[pos-1] (.) B.tables[pos] / P                  table.rs:320-345, 500-505
 //   to_mapping_by_score_ratio                                          hint.rs:135-142, table.rs:134-149
 //
@@ -41,10 +42,18 @@ struct LeanBwdShared {
     double etot[64];      // totals of the record's entries (B-list selection)
     uint8_t tgt[64];      // lane that received entry j
     uint8_t slot_of[64];  // per lane: record slot of its entry (0xff: none)
+    double init[64];      // per lane: BwdAdj.init of its node, parked here when its record arrives
+    // InsBegin of the column on the lanes, in its scale 2^Eprev (b_init: 0), as the sum of acc[0..64).  The chain
+    // ib = S + p_II p_r ib' (S: sum over the list, backward.rs:535-555) is linear, so each lane carries its own share of
+    // it: no cross-lane sum per position (only at a hand-off), and no register through the loop (it has none to spare)
+    double acc[64];
+    // the chain's constants p_II p_r, p_IM p_match, p_IM p_mismatch, p_ID: read from here at each use (kept in registers,
+    // as the compiler would hoist them, they would be live through the whole position loop)
+    double kc[4];
 };
 
 __device__ __forceinline__ void lb_park(const SparseBwdArgs &a, uint32_t gi, bool inprev, uint32_t id, double m, double i, double d,
-                                        int E) {
+                                        int E, double ib) {
     // B column -> hand-off slot (list form)
     BHandoff &h = a.hand[gi];
     const unsigned long long mask = __ballot(inprev);
@@ -52,6 +61,7 @@ __device__ __forceinline__ void lb_park(const SparseBwdArgs &a, uint32_t gi, boo
     if (threadIdx.x == 0) {
         h.n = n;
         h.E = E;
+        h.ib = ib;
     }
     if (inprev) {
         const int s = __popcll(mask & ((1ull << threadIdx.x) - 1ull));
@@ -241,6 +251,13 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
         }
     };
 
+    if (lane == 0) {
+        sh.kc[0] = lp.p_II * lp.p_random;
+        sh.kc[1] = lp.p_IM * lp.p_match;
+        sh.kc[2] = lp.p_IM * lp.p_mismatch;
+        sh.kc[3] = lp.p_ID;
+    }
+    ln_sync();
     Hdr hcur{};
     if (a.mode == 0) {
         pos = len - 1;
@@ -273,8 +290,10 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
                     pd = h.d[lane];
                     inprev = true;
                     R = a.M.badj[id];
+                    sh.init[lane] = R.init;
                 }
                 Eprev = h.E;
+                sh.acc[lane] = lane == 0 ? h.ib : 0.0;
                 have_col = true;
             }
         } else {
@@ -356,7 +375,6 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
         const int slot = sh.slot_of[lane] == 0xff ? -1 : (int)sh.slot_of[lane];
         PROFB_T(1)
         const Ent mine = entry(pos - 1, hcur, slot < 0 ? 0 : slot, slot >= 0);
-        const double fm = mine.m, fi = mine.i, fd = mine.d;
         bool sel = false;  // member of the B list: one of the `na` largest totals (ties: record order)
         // ---- nodes new to the column take their lanes; the record of ONE new node that was foreseen comes out of LDS,
         // anything else from memory (then every memory operation of the wave is waited for)
@@ -369,9 +387,15 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
                 const bool foreseen = (newm & (newm - 1ull)) == 0ull && key1 == ahead;
                 if (foreseen) {
                     vm_wait_upto(vm_issued - rq_adj);
-                    if (isnew) R = *(const BwdAdj *)sh.stage;
+                    if (isnew) {
+                        R = *(const BwdAdj *)sh.stage;
+                        sh.init[lane] = ((const BwdAdj *)sh.stage)->init;
+                    }
                 } else {
-                    if (isnew) R = a.M.badj[mine.id];
+                    if (isnew) {
+                        R = a.M.badj[mine.id];
+                        sh.init[lane] = a.M.badj[mine.id].init;
+                    }
                     vm_drain();
                 }
                 if (isnew) {
@@ -454,6 +478,10 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
         }
         const double iv = prev_is_init ? pend : (inprev ? pi : 0.0);
         const double qq = lp.p_random * iv;
+        // ---- bib, first half, in the previous column's scale: p_II p_r ib' + init_l p_IM e_l(x) m'[l] -- the node's own m'[l]
+        // is the lane's previous value, init_l came with its record (sh.init)
+        sh.acc[lane] = (prev_is_init ? 0.0 : sh.kc[0] * sh.acc[lane]) +
+                       (sel ? sh.init[lane] * sh.kc[R.emis == x ? 1 : 2] * (prev_is_init ? pend : pm) : 0.0);
         double dsum = sel ? lp.p_DM * a1 + lp.p_DI * qq : 0.0;
         double lv = dsum;
         // ---- bdt (backward.rs:387-404), restricted to the list
@@ -494,7 +522,10 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
         // 2^(E_F + E_B) / P with P = 2^-kP e^-rP split once per read: a power of two per position, no exp
         const int ew = hcur.E + Ecur + kP;
         const double w = !ok ? 0.0 : ((ew > -1000 && ew < 1000) ? cP * sp_pow2(ew) : exp((double)(hcur.E + Ecur) * SP_LN2 - logP));
-        const double val = (slot >= 0 && sel) ? w * (fm * bm + fi * bi + fd * bd) : 0.0;
+        // (the entry's m / i / d are read again here, from the ring slot, which stays put until the request of position
+        // pos-5: six registers less through the column step -- room for the begin-state chain)
+        const Ent fe = entry(pos - 1, hcur, slot < 0 ? 0 : slot, slot >= 0);
+        const double val = (slot >= 0 && sel) ? w * (fe.m * bm + fe.i * bi + fe.d * bd) : 0.0;
         PROFB_T(5)
         if (!emit(pos - 1, slot >= 0, id, val)) {
             err |= SP_ERR_POOL;
@@ -511,6 +542,8 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
             pm = pi = pd = 0.0;
             inprev = false;
         }
+        // ---- bib, second half: into the new column's scale, + init_l p_ID d[l] (the list's lanes are now those with inprev)
+        sh.acc[lane] = sh.acc[lane] * sp_pow2(-e) + (inprev ? sh.init[lane] * sh.kc[3] * pd : 0.0);
         Eprev = Ecur;
         prev_is_init = false;
         have_col = true;
@@ -525,7 +558,7 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no fetch-ahead may outlive the wave's use of LDS
     // ---- leave: park the column for the next phase, or hand it to the dense backward kernel
     if (stopped && !err) {
-        if (have_col && stop_at < len) lb_park(a, gi, inprev, id, pm, pi, pd, Eprev);
+        if (have_col && stop_at < len) lb_park(a, gi, inprev, id, pm, pi, pd, Eprev, wave_sum(sh.acc[lane]));
         if (lane == 0) a.stop[gi] = stop_at;
     } else if (!err) {
         if (have_col) {
@@ -542,9 +575,11 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
                 mx = fmax(pm, pi);
             }
             mx = wave_max(mx);
+            const double ib = wave_sum(sh.acc[lane]);
             if (lane == 0) {
                 a.d.cmaxB[((size_t)g * a.d.Lc + (s0 + 1)) * a.W + r] = (unsigned long long)__double_as_longlong(mx);
                 a.d.BE[((size_t)g * (a.d.Lc + 1) + (s0 + 1)) * a.W + r] = Eprev;
+                a.d.logibB[((size_t)g * (a.d.Lc + 1) + (s0 + 1)) * a.W + r] = log(ib) + (double)Eprev * SP_LN2;
             }
         }
         if (lane == 0) a.stop[gi] = s0;

@@ -157,6 +157,8 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
     const bool ok = logP > -INFINITY;
     int pos;            // next position to compute
     int have_cols = 0;  // cols[(pos+1)&1] holds B.tables[pos+1]
+    double ib = 0.0;    // InsBegin of B.tables[pos+1], in its column's scale (b_init: 0)
+    double mb = 0.0;    // MatchBegin of the column computed last, same scale
     bool stopped = false;
     int stop_at = 0;
     if (a.mode == 0) {
@@ -184,6 +186,7 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
                 c.n = c.na = n;
                 c.E = h.E;
             }
+            ib = h.ib;
             wave_sync();
             for (int j = lane; j < n; j += 64) {
                 c.id[j] = h.id[j];
@@ -197,9 +200,12 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
         }
     }
     int steps_done = 0;
-    for (; !stopped && pos >= s0 + 1 && !err; pos--) {
+    // list mode walks on to position 0: B.tables[0] over mapping.nodes(0) (backward.rs:59-90) -- no forward record,
+    // no mapping to emit, only its begin state mb (the read's backward total)
+    const int pos_end = a.list_off ? 0 : s0 + 1;
+    for (; !stopped && pos >= pos_end && !err; pos--) {
         // B.tables[pos] over filled_nodes(F.tables[pos-1]) (backward.rs:122-129)
-        if (!load_record<CAP>(a.fpool, p0 + (uint64_t)(pos - 1), fr)) {
+        if (pos > 0 && !load_record<CAP>(a.fpool, p0 + (uint64_t)(pos - 1), fr)) {
             stopped = true;  // the forward record is larger than this class
             stop_at = pos;
             break;
@@ -224,8 +230,12 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
         wave_sync();
         Col<CAP> &prev = cols[(pos + 1) & 1];
         Col<CAP> &cur = cols[pos & 1];
-        bwd_list_step<CAP>(a.M, prev, pos == len - 1, cur, list, nl, a.bases[((size_t)g * a.Lb + pos) * a.W + r], dA, dB);
+        const BeginStates bs =
+            bwd_list_step<CAP>(a.M, prev, pos == len - 1, cur, list, nl, a.bases[((size_t)g * a.Lb + pos) * a.W + r], dA, dB, ib);
+        ib = bs.ib;
+        mb = bs.mb;
         have_cols = 1;
+        if (pos == 0) break;  // (list mode) column 0 has no F.tables[-1]: nothing to emit
         // S = F.tables[pos-1] (.) B.tables[pos] / P over F's elements (table.rs:320-345, 500-505)
         const double w = ok ? exp((double)(fr.E + cur.E) * SP_LN2 - logP) : 0.0;
         for (int j = lane; j < fr.n; j += 64) {
@@ -245,6 +255,9 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
     if (a.list_off) {
         if (stopped) err |= SP_ERR_CAPACITY;  // a forward record is missing or larger than the list class
         if (lane == 0) a.stop[gi] = stopped ? stop_at : s0;
+        // ln B.tables[0].mb (column 0 is the one computed last)
+        if (a.logb && lane == 0 && have_cols && !stopped && !err)
+            a.logb[gi] = log(mb) + (double)cols[0].E * SP_LN2;
     } else if (stopped && !err) {
         // park B.tables[stop_at + 1] for the next phase
         if (have_cols && stop_at < len) {
@@ -255,6 +268,7 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
                 if (lane == 0) {
                     h.n = c.n;
                     h.E = c.E;
+                    h.ib = ib;  // the column parked is the one computed last (or the one taken over)
                 }
                 for (int j = lane; j < c.n; j += 64) {
                     h.id[j] = c.id[j];
@@ -286,6 +300,8 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
             if (lane == 0) {
                 a.d.cmaxB[((size_t)g * a.d.Lc + (s0 + 1)) * a.W + r] = (unsigned long long)__double_as_longlong(mx);
                 a.d.BE[((size_t)g * (a.d.Lc + 1) + (s0 + 1)) * a.W + r] = c.E;
+                // its InsBegin, natural log, for the dense head's begin-state chain (bwd_chain, dense.hip)
+                a.d.logibB[((size_t)g * (a.d.Lc + 1) + (s0 + 1)) * a.W + r] = log(ib) + (double)c.E * SP_LN2;
             }
         }
         if (lane == 0) a.stop[gi] = s0;
@@ -779,6 +795,12 @@ __global__ void __launch_bounds__(BLOCK) emit_dense_map(const DenseMapArgs ma, c
     if (threadIdx.x == 0) cnt[gi] = 0;
 }
 
+// ln B.tables[0].mb of every lane of the chunk: row 0 of logmbB ([ng][Lc+1][W]) in lane order
+__global__ void __launch_bounds__(BLOCK) gather_logb(const double *logmbB, int Lc, int W, int lanes, double *out) {
+    const int gi = blockIdx.x * BLOCK + threadIdx.x;
+    if (gi < lanes) out[gi] = logmbB[(size_t)(gi / W) * (Lc + 1) * W + gi % W];
+}
+
 __global__ void __launch_bounds__(BLOCK) merge_logp(const uint32_t *lanes, int n, const double *src, double *dst) {
     const int j = blockIdx.x * BLOCK + threadIdx.x;
     if (j < n) dst[lanes[j]] = src[lanes[j]];
@@ -843,7 +865,7 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
                  o_an = carve(sizeof(uint32_t) * (size_t)lanes * KMAX * 2), o_av = carve(sizeof(double) * (size_t)lanes * KMAX * 2),
                  o_hand = carve(sizeof(BHandoff) * (size_t)lanes), o_eoff = carve(sizeof(unsigned long long) * 2 * (size_t)lanes),
                  o_wls = carve(sizeof(uint32_t) * 2 * (size_t)lanes), o_wlb = carve(sizeof(uint32_t) * 2 * (size_t)lanes),
-                 o_wlc = carve(sizeof(int) * 2);
+                 o_wlc = carve(sizeof(int) * 2), o_lb = carve(sizeof(double) * (size_t)lanes);
     ctl.reserve(cb);
     char *cp = (char *)ctl.p;
     // Pa (two buffers, by position parity), the per-run maxima of Pa, and Pb -- the plane of merged index `len`, which
@@ -1050,11 +1072,21 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
         for (int par = 0; par < 2; par++)
             if (emitted[par]) HIP_CHECK(hipStreamWaitEvent(s, ev_emit[par], 0));
         HIP_CHECK(hipGetLastError());
+        // begin states of column 0 (backward.rs:499-555): ln B.tables[0].mb = the read's backward total
+        // (to_full_prob_backward, table.rs:492-494); logmbB is [ng][Lc+1][W], row 0 of every group
+        const bool want_lb = mc.logb_out && pos_max >= 0 && lanes > 0;
+        if (want_lb) {
+            launch_bwd_finish(W, a);
+            hipLaunchKernelGGL(gather_logb, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, (const double *)a.logmbB,
+                               a.Lc, W, lanes, (double *)(cp + o_lb));
+            HIP_CHECK(hipGetLastError());
+        }
         st.ms[1] += lt.total_ms();
         for (int gi = 0; gi < lanes; gi++)
             if (st_on && hb[gi] >= 0) st.cells[1] += (uint64_t)((hb[gi] & ~(1 << 30)) + 1) * m->N;
         std::vector<uint32_t> herr(lanes);
         HIP_CHECK(hipMemcpyAsync(herr.data(), cp + o_err, sizeof(uint32_t) * lanes, hipMemcpyDeviceToHost, s));
+        if (want_lb) HIP_CHECK(hipMemcpyAsync(mc.logb_out, cp + o_lb, sizeof(double) * lanes, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         if (dense_lock.owns_lock()) dense_lock.unlock();
         trace("  dense backward+collect");
@@ -1177,7 +1209,7 @@ static void init_sink(phmm_model *m, const phmm_reads *reads, MappingSink &sink,
 }
 
 static void finish_mappings(phmm_model *m, const phmm_reads *reads, MappingSink &sink, const std::vector<double> &lf,
-                            phmm_mappings **out, double *out_node_freq) {
+                            const std::vector<double> &lb, phmm_mappings **out, double *out_node_freq) {
     hipStream_t s = current_stream();
     const uint64_t n_pos = reads->total;
     std::unique_ptr<phmm_mappings> mp(new phmm_mappings());
@@ -1185,6 +1217,7 @@ static void finish_mappings(phmm_model *m, const phmm_reads *reads, MappingSink 
     mp->total_pos = n_pos;
     mp->read_off = reads->off;
     mp->read_logp = lf;
+    mp->read_logp_backward = lb;
     mp->host_valid = false;
     mp->trusted = true;
     (void)hipGetDevice(&mp->device);
@@ -1251,12 +1284,12 @@ static void finish_mappings(phmm_model *m, const phmm_reads *reads, MappingSink 
 void generate_mappings_sparse(phmm_model *m, const phmm_reads *reads, phmm_mappings **out, double *out_node_freq,
                               bool by_ratio) {
     MappingSink sink{};
-    std::vector<double> lf(reads->R);
+    std::vector<double> lf(reads->R), lb(reads->R);
     double tot = 0.0;
     for (int attempt = 0;; attempt++) {
         init_sink(m, reads, sink, by_ratio ? 0 : (int)m->params.n_active_nodes);
         try {
-            full_prob_reads_sparse(m, reads, lf.data(), &tot, &sink, by_ratio);
+            full_prob_reads_sparse(m, reads, lf.data(), &tot, &sink, by_ratio, lb.data());
             break;
         } catch (const SinkOverflow &) {
             if (attempt >= 4) PHMM_THROW(PHMM_ENOMEM, "mapping pool keeps overflowing");
@@ -1265,7 +1298,7 @@ void generate_mappings_sparse(phmm_model *m, const phmm_reads *reads, phmm_mappi
         }
     }
     trace("forward+backward chunks");
-    finish_mappings(m, reads, sink, lf, out, out_node_freq);
+    finish_mappings(m, reads, sink, lf, lb, out, out_node_freq);
 }
 
 // ---------------------------------------------------------------- Mapping::map_nodes
@@ -1463,8 +1496,9 @@ void mappings_map_nodes(phmm_model *m, const phmm_reads *reads, const phmm_mappi
     if (herr & 4) PHMM_THROW(PHMM_EINTERNAL, "map_nodes: output pool exhausted");
     std::vector<double> lf = mp_in->read_logp;
     if (lf.size() != reads->R) lf.assign(reads->R, 0.0);
-    finish_mappings(m, reads, sink, lf, out, nullptr);
+    finish_mappings(m, reads, sink, lf, mp_in->read_logp_backward, out, nullptr);
     if (mp_in->read_logp.size() != reads->R) (*out)->read_logp.clear();
+    if (mp_in->read_logp_backward.size() != reads->R) (*out)->read_logp_backward.clear();
 }
 
 // PHMMModel::generate_mappings(reads, Some(mappings), use_max_ratio): run_with_mapping
@@ -1513,7 +1547,7 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
     };
     const size_t o_len = carve(sizeof(int) * R), o_sw = carve(sizeof(int) * R), o_stop = carve(sizeof(int) * R),
                  o_err = carve(sizeof(uint32_t) * R), o_lanes = carve(sizeof(uint32_t) * R), o_logp = carve(sizeof(double) * R),
-                 o_bases = carve((size_t)R * Lb), o_hand = carve(sizeof(BHandoff));
+                 o_logb = carve(sizeof(double) * R), o_bases = carve((size_t)R * Lb), o_hand = carve(sizeof(BHandoff));
     ctl.reserve(cb);
     char *cp = (char *)ctl.p;
     HIP_CHECK(hipMemsetAsync(cp, 0, o_bases, s));
@@ -1548,6 +1582,7 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
     ba.mode = 0;
     ba.stop = (int *)(cp + o_stop);
     ba.hand = (BHandoff *)(cp + o_hand);
+    ba.logb = (double *)(cp + o_logb);
     std::vector<uint32_t> cls[2];
     for (uint64_t r = 0; r < R; r++) cls[mp_in->read_max_list[r] <= 64 ? 0 : 1].push_back((uint32_t)r);
     for (int attempt = 0;; attempt++) {
@@ -1576,7 +1611,10 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
         sink.mp.base = m->wset().aux[5].as<uint8_t>();
         sink.mp.cap = sink.cap;
     }
-    finish_mappings(m, reads, sink, lf, out, out_node_freq);
+    // backward_with_mapping's totals, ln B.tables[0].mb (the list kernels' last step)
+    std::vector<double> lb(R);
+    HIP_CHECK(hipMemcpy(lb.data(), ba.logb, sizeof(double) * R, hipMemcpyDeviceToHost));
+    finish_mappings(m, reads, sink, lf, lb, out, out_node_freq);
 }
 
 }  // namespace phmm

@@ -222,6 +222,7 @@ struct alignas(16) BwdAdj {   // backward: sums over children
     uint8_t chi_emis[ADJ_DEG];
     uint8_t emis, nchi, over;
     uint32_t par0;            // first parent (0xffffffff: none): the node a backward column takes in next on a unitig
+    double init;              // Begin -> this node (the model's own): the Begin-state sums bmb / bib (backward.rs:499-555)
 };
 // Topology-only record of the hinted forward (candidate batches bring their own init / trans): parents with the
 // ids of their edges, so that trans[candidate][edge] is one dependent load behind the record.
@@ -302,6 +303,7 @@ struct phmm_mappings {
     std::vector<double> logp;
     std::vector<uint32_t> read_max_list;  // [R] longest node list of each read
     std::vector<double> read_logp;        // [R] ln P(read) of the forward pass that produced the mappings (may be empty)
+    std::vector<double> read_logp_backward;  // [R] ln B.tables[0].mb of the backward pass of the same call (may be empty)
     mutable phmm::DevBuf d_pos_off, d_nodes, d_logp;
     int device = -1;  // >= 0: the device whose pool takes the buffers back (phmm_mappings_destroy)
     mutable bool on_device = false;
@@ -415,7 +417,7 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
 struct MappingSink;
 // by_ratio: use_max_ratio of forward_sparse (forward.rs:93-154); false = fixed warm-up + top n_active_nodes
 void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_logp, double *out_total,
-                            MappingSink *sink, bool by_ratio = true);
+                            MappingSink *sink, bool by_ratio = true, double *out_logb = nullptr);
 void generate_mappings_sparse(phmm_model *m, const phmm_reads *reads, phmm_mappings **out, double *out_node_freq,
                               bool by_ratio = true);
 void ensure_logib(phmm_model *m, size_t len);

@@ -311,13 +311,19 @@ __device__ uint32_t fwd_list_step(const SparseModel &M, const Col<CAP> &prev, Co
 // ---------------------------------------------------------------------------------
 // One backward column over a GIVEN node list (non-adaptive b_step, backward.rs:216-261 with
 // is_adaptive = false: backward_with_mapping / backward_by_forward, backward.rs:59-142):
-//   bd = bd0 + G x bdt restricted to the list (299-404), bm (423-444), bi (462-483);
-//   the begin states bmb/bib are not needed by the mapping flow and are left out.
+//   bd = bd0 + G x bdt restricted to the list (299-404), bm (423-444), bi (462-483), and the begin states
+//   bmb / bib over the list (499-555):
+//     bmb = sum_l init_l (p_MM e_l(x) m'[l] + p_MD d[l]) + p_MI p_r ib',   bib: p_IM, p_ID, p_II
 // prev: the column of position pos+1; prev_is_init: it is b_init (m = i = d = p_end for every
-// node, backward.rs:197-211).  list may live in LDS or global memory.
+// node, ib = 0, backward.rs:197-211).  list may live in LDS or global memory.
+// ib_in: InsBegin of prev in prev's scale (ignored for b_init, whose ib is 0).  Returns cur's begin states in cur's
+// scale (scaled-linear like the column: no log per position).
+struct BeginStates {
+    double ib, mb;
+};
 template <int CAP>
-__device__ void bwd_list_step(const SparseModel &M, const Col<CAP> &prev, bool prev_is_init, Col<CAP> &cur,
-                              const uint32_t *list, int n, uint8_t x, double *dA, double *dB) {
+__device__ BeginStates bwd_list_step(const SparseModel &M, const Col<CAP> &prev, bool prev_is_init, Col<CAP> &cur,
+                                     const uint32_t *list, int n, uint8_t x, double *dA, double *dB, double ib_in) {
     // in-list child links cached in LDS by the bd0 pass (small classes only): the n_max_gaps Del
     // sweeps and the bm/bi pass then need no global (CSR) access at all
     constexpr bool LINKS = CAP <= 128;
@@ -340,6 +346,7 @@ __device__ void bwd_list_step(const SparseModel &M, const Col<CAP> &prev, bool p
     }
     wave_sync();
     const double pend = lp.p_end;
+    double sm = 0.0, sd = 0.0;  // this lane's share of sum_l init_l e_l(x) m'[l] and of sum_l init_l d[l]
     // bd0 (backward.rs:354-377); keep A1 = sum_w t e_w m'[w] and q0 = p_r i'[v] for bm/bi
     for (int j = threadIdx.x; j < n; j += 64) {
         const uint32_t v = cur.id[j];
@@ -369,12 +376,16 @@ __device__ void bwd_list_step(const SparseModel &M, const Col<CAP> &prev, bool p
         }
         if (LINKS)
             for (int q = nl; q < LPN; q++) lk_slot[j * LPN + q] = -1;
-        double iv = 0.0;
-        if (prev_is_init) iv = pend;
+        double iv = 0.0, mv = 0.0;
+        if (prev_is_init) iv = mv = pend;
         else {
             const int os = hash_find(prev, v);
-            if (os >= 0) iv = prev.i[os];
+            if (os >= 0) {
+                iv = prev.i[os];
+                mv = prev.m[os];
+            }
         }
+        sm += M.init[v] * (M.emis[v] == x ? lp.p_match : lp.p_mismatch) * mv;
         const double q0 = lp.p_random * iv;
         const double d0 = lp.p_DM * a1 + lp.p_DI * q0;
         cur.m[j] = a1;  // stash
@@ -437,10 +448,19 @@ __device__ void bwd_list_step(const SparseModel &M, const Col<CAP> &prev, bool p
         const double a1 = cur.m[j], q0 = cur.i[j], td = dA[j];
         cur.m[j] = lp.p_MM * a1 + lp.p_MD * td + lp.p_MI * q0;
         cur.i[j] = lp.p_IM * a1 + lp.p_ID * td + lp.p_II * q0;
+        sd += M.init[cur.id[j]] * cur.d[j];
     }
+    // begin states in prev's scale (the column's own values before its rescale)
+    const double SM = wave_sum(sm), SD = wave_sum(sd);
+    const double ibp = prev_is_init ? 0.0 : ib_in;
+    const double ibn = lp.p_IM * SM + lp.p_ID * SD + lp.p_II * lp.p_random * ibp;
+    const double mbn = lp.p_MM * SM + lp.p_MD * SD + lp.p_MI * lp.p_random * ibp;
     wave_sync();
-    col_rescale(cur, prev_is_init ? 0 : prev.E, 0.0);
+    const int E_in = prev_is_init ? 0 : prev.E;
+    col_rescale(cur, E_in, 0.0);
     wave_sync();
+    const double sc = sp_pow2(E_in - cur.E);
+    return BeginStates{ibn * sc, mbn * sc};
 }
 
 // fe (forward.rs:554-558): ln(p_end * sum over the active list of m+i+d) + E ln2

@@ -120,6 +120,7 @@ namespace phmm {
 static constexpr int HANDOFF_CAP = 128;
 struct BHandoff {
     int n, E;
+    double ib;  // InsBegin of the column, same scale as m / i / d (true value = ib * 2^E)
     uint32_t id[HANDOFF_CAP];
     double m[HANDOFF_CAP], i[HANDOFF_CAP], d[HANDOFF_CAP];
 };
@@ -145,6 +146,9 @@ struct SparseBwdArgs {
                      // kernels anywhere -- their err carries SP_STOP_SLICE --, the 400-slot kernel where it fits 64 nodes)
     int *stop;       // [lanes] in (mode 1): position to compute next; out: see below
     BHandoff *hand;  // [lanes]
+    // list mode: ln B.tables[0].mb per lane (to_full_prob_backward, table.rs:492-494) -- one more list step over
+    // mapping.nodes(0) after position 1, Begin sums only.  (Adaptive mode: the dense head has column 0.)
+    double *logb;    // [lanes] or null
 };
 // stop[gi] on exit: s0      -> finished (column s0+1 handed to the dense kernel)
 //                   len     -> nothing done (the record of the last position does not fit the class)
@@ -182,6 +186,7 @@ struct MapChunk {
     double *cand_tot;
     int topk;  // > 0: to_mapping(topk) instead of to_mapping_by_score_ratio
     std::mutex *dense_token;  // held while the chunk runs its HBM-bound dense backward (sparse_dyn.hip)
+    double *logb_out;  // [lanes] host, or null: ln B.tables[0].mb of every lane (the backward total of its read)
     bool main_plan;  // per-launch statistics (bench.py's roofline) cover the main plan's full-width launches only
 };
 

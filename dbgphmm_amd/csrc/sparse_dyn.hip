@@ -344,7 +344,7 @@ void launch_col_count_w(int W, const WarmArgs &wa, int col) {
 
 // PHMMModel::to_full_prob_reads without mappings: forward_sparse_score_only(use_max_ratio = true)
 void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_logp, double *out_total,
-                            MappingSink *sink, bool by_ratio) {
+                            MappingSink *sink, bool by_ratio, double *out_logb) {
     stats() = CallStats();
     const uint64_t R = reads->R;
     if (m->dev.max_degree > 8)
@@ -352,6 +352,7 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
     ensure_logib(m, reads->max_len + 1);
     const phmm_params &prm = m->params;
     std::vector<double> lf(R, 0.0);
+    std::vector<double> lb(out_logb ? R : 0, 0.0);  // (with a sink) backward totals of backward_by_forward
     std::vector<uint16_t> new_hint(R, 0);
     std::vector<uint32_t> new_flags(R, 0);  // PHMM_READ_* (written by the chunk that owns the read; chunks are disjoint)
     upload_reads(reads);
@@ -677,6 +678,7 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
         std::vector<int> hsw(lanes);
         std::vector<int> hcn(lanes);
         std::vector<double> tlf(lanes);
+        std::vector<double> tlb(lanes, 0.0);
         HIP_CHECK(hipMemcpyAsync(hsw.data(), wa.sw, sizeof(int) * lanes, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipMemcpyAsync(hcn.data(), wa.cand_n, sizeof(int) * lanes, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipMemcpyAsync(tlf.data(), a.logPf, sizeof(double) * lanes, hipMemcpyDeviceToHost, s));
@@ -928,6 +930,7 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
                 mc.cand_tot = wa.cand_tot;
                 mc.dense_token = use_token ? &dense_token : nullptr;
                 mc.main_plan = it.pc->may_defer || !by_ratio;
+                mc.logb_out = out_logb ? tlb.data() : nullptr;
                 trace("sparse forward");
                 mapping_backward_chunk(mc, sparse_lanes, sink, plan, g0, R);
                 trace("mapping backward total");
@@ -958,6 +961,7 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
             mc.cand_tot = wa.cand_tot;
                 mc.dense_token = use_token ? &dense_token : nullptr;
                 mc.main_plan = it.pc->may_defer || !by_ratio;
+            mc.logb_out = out_logb ? tlb.data() : nullptr;
             mapping_backward_chunk(mc, sparse_lanes, sink, plan, g0, R);
         }
         for (int gi = 0; gi < lanes; gi++) {
@@ -965,6 +969,7 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
             if (slot >= R || hl[gi] == 0) continue;
             const uint32_t rd = plan.order[slot];
             lf[rd] = hsw[gi] < hl[gi] ? slp[gi] : tlf[gi];
+            if (out_logb && sink) lb[rd] = tlb[gi];
             new_hint[rd] = (uint16_t)std::min(hsw[gi], 65535);
         }
         }
@@ -1091,6 +1096,7 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
     for (uint64_t r = 0; r < R; r++) tot += lf[r];
     put_doubles(out_logp, lf.data(), R);
     put_doubles(out_total, &tot, 1);
+    if (out_logb) std::copy(lb.begin(), lb.end(), out_logb);
 }
 
 }  // namespace phmm

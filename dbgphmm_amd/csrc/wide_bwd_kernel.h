@@ -37,6 +37,8 @@ struct WideBwdShared {
     uint32_t list[512];
     double red[2][8];
     int wsum[2][8];
+    double bterm[WBK_T];  // per slot: its term of bib's sum over the list, init_v (p_IM e_v(x) m'[v] + p_ID d[v])
+    double ib[2];         // InsBegin of B.tables[p], in its column's scale, by the parity of p
     unsigned long long bc;
     LinParams lp;  // (read from here: the scalar registers are short)
 };
@@ -190,7 +192,7 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
     int par = 0;
     const bool ok = logP > -INFINITY;
     int pos;            // next position to compute
-    int have_cols = 0;  // col[(pos+1)&1] holds B.tables[pos+1]
+    int have_cols = 0;  // col[(pos+1)&1] holds B.tables[pos+1] (and sh.ib[(pos+1)&1] its InsBegin)
     bool stopped = false;
     int stop_at = 0;
     int fn = 0, fna = 0, fE = 0;
@@ -217,6 +219,7 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
             if (t == 0) {
                 c.n = n;
                 c.E = h.E;
+                sh.ib[(pos + 1) & 1] = h.ib;
             }
             __syncthreads();
             if (t < n) {
@@ -290,13 +293,19 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
                 a1 += w * (rec.chi_emis[q] == x ? lp.p_match : lp.p_mismatch) * mu;
                 cs[q] = wb_find(cur, u);
             }
-            double iv = 0.0;
-            if (prev_is_init) iv = pend;
+            double iv = 0.0, mv = 0.0;
+            if (prev_is_init) iv = mv = pend;
             else {
                 const int os = wb_find(prev, cur.id[t]);
-                if (os >= 0) iv = prev.i[os];
+                if (os >= 0) {
+                    iv = prev.i[os];
+                    mv = prev.m[os];
+                }
             }
             qq = lp.p_random * iv;
+            // bib (backward.rs:535-555), the m' half of this node's term: the node's own m'[v] sits in the slot the Ins term
+            // just found; the d half is added at the rescale
+            sh.bterm[t] = lp.p_IM * rec.init * (rec.emis == x ? lp.p_match : lp.p_mismatch) * mv;
             const double d0 = lp.p_DM * a1 + lp.p_DI * qq;
             cur.d[t] = d0;
             sh.dA[t] = d0;
@@ -339,10 +348,23 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
             cur.m[t] = nm * sc;
             cur.i[t] = ni * sc;
             cur.d[t] = nd * sc;
+            sh.bterm[t] = (sh.bterm[t] + lp.p_ID * rec.init * nd) * sc;
         }
         if (t == 0) cur.E = Ecur;
         __syncthreads();
         have_cols = 1;
+        // bib = sum over the list of the terms + p_II p_r ib', in the column's scale, by wave 0 alone (its lane j adds the
+        // slots j, j+64, ...): no block reduction, no barrier of its own
+        if (t < 64) {  // (wave 0: the next barrier publishes sh.ib[pos & 1])
+            double part = 0.0;
+#pragma unroll 1
+            for (int w = 0; w < WBK_WAVES; w++) {
+                const int k = t + 64 * w;
+                if (k < nl) part += sh.bterm[k];
+            }
+            const double ib = wave_sum(part) + lp.p_II * lp.p_random * (prev_is_init ? 0.0 : sh.ib[(pos + 1) & 1]) * sc;
+            if (t == 0) sh.ib[pos & 1] = ib;
+        }
         // S = F.tables[pos-1] (.) B.tables[pos] / P over F's elements (table.rs:320-345, 500-505)
         const double w = ok ? exp((double)(fE + Ecur) * SP_LN2 - logP) : 0.0;
         if (t < fn) {
@@ -368,6 +390,7 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
                 if (t == 0) {
                     h.n = c.n;
                     h.E = c.E;
+                    h.ib = sh.ib[(stop_at + 1) & 1];
                 }
                 if (t < c.n) {
                     h.id[t] = c.id[t];
@@ -396,6 +419,8 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
             if (t == 0) {
                 a.d.cmaxB[((size_t)g * a.d.Lc + (s0 + 1)) * a.W + r] = (unsigned long long)__double_as_longlong(mx);
                 a.d.BE[((size_t)g * (a.d.Lc + 1) + (s0 + 1)) * a.W + r] = c.E;
+                // its InsBegin, natural log, for the dense head's begin-state chain (bwd_chain, dense.hip)
+                a.d.logibB[((size_t)g * (a.d.Lc + 1) + (s0 + 1)) * a.W + r] = log(sh.ib[(s0 + 1) & 1]) + (double)c.E * SP_LN2;
             }
         }
         if (t == 0) a.stop[gi] = s0;

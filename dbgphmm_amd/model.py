@@ -110,6 +110,14 @@ class Mappings:
         _ffi.check(_ffi.lib().phmm_mappings_read_logp(self._h, _ptr(lp), _ptr(tot)))
         return float(tot[0]), lp
 
+    def read_logp_backward(self, out_logp=None):
+        """ln P(read) of the backward pass that produced these mappings (B.tables[0].mb,
+        PHMMOutput::to_full_prob_backward) -> (total, per read)."""
+        lp = np.empty(len(self.reads)) if out_logp is None else out_logp
+        tot = np.empty(1)
+        _ffi.check(_ffi.lib().phmm_mappings_read_logp_backward(self._h, _ptr(lp), _ptr(tot)))
+        return float(tot[0]), lp
+
     def map_nodes(self, model_after: "PHMMModel", map_off: np.ndarray, map_nodes: np.ndarray) -> "Mappings":
         """Mapping::map_nodes (hint.rs:60-88) for every read: carry the lists over to another graph through a
         node map given as CSR over this mapping's graph (MultiDbg::hint_kp1_from_hint_k,

@@ -173,6 +173,13 @@ int phmm_mappings_node_freqs(const phmm_mappings *mp, uint32_t n_nodes, double *
  * that produced `mp` in phmm_generate_mappings: PHMMOutput::to_full_prob_forward per read.
  * out_logp[R] / out_total (their sum) may be NULL or device pointers. */
 int phmm_mappings_read_logp(const phmm_mappings *mp, double *out_logp, double *out_total);
+/* ln P(read) of the backward pass of the same call: B.tables[0].mb, PHMMOutput::to_full_prob_backward per read
+ * (table.rs:492-494) -- backward_by_forward (backward.rs:101-142) without input mappings, backward_with_mapping
+ * (backward.rs:59-90) with them; begin states as in backward.rs:499-555.  Equal to phmm_mappings_read_logp up to
+ * the mass the truncated frontier lost: the gap is the reference's own self-check of a read.
+ * out_logp[R] / out_total (their sum) may be NULL or device pointers.  PHMM_EINVAL for mappings not produced by
+ * phmm_generate_mappings (phmm_mappings_map_nodes carries the values over). */
+int phmm_mappings_read_logp_backward(const phmm_mappings *mp, double *out_logp, double *out_total);
 void phmm_mappings_destroy(phmm_mappings *mp);
 
 /* ---- read-set likelihood ------------------------------------------------------
@@ -240,7 +247,7 @@ int phmm_backward_sparse_tables(phmm_model *m, const uint8_t *read, uint64_t len
  * nothing).  The node map is a CSR over the nodes of the graph the mappings were made on:
  * images of node v = map_nodes[map_off[v] .. map_off[v+1]) (ids of `model_after`'s nodes; may be empty).
  * Per position: prob(image) += prob(node) / |images(node)|, then the 400 most probable, descending.
- * read_logp of the result is copied from `mappings`. */
+ * read_logp and read_logp_backward of the result are copied from `mappings`. */
 int phmm_mappings_map_nodes(phmm_model *model_after, const phmm_reads *reads,
                             const phmm_mappings *mappings, const uint32_t *map_off,
                             const uint32_t *map_nodes, uint32_t n_nodes_before,

@@ -161,6 +161,21 @@ impl AmdMappings {
         }
         Mappings::new(out)
     }
+    /// ln P of every read by the forward pass that produced these mappings (PHMMOutput::to_full_prob_forward,
+    /// table.rs:482-491) -> (total, per read).  Mappings from `generate_mappings` only.
+    pub fn read_logp(&self, reads: &AmdReads) -> (f64, Vec<f64>) {
+        let (mut total, mut per) = (0f64, vec![0f64; reads.n_reads()]);
+        check(unsafe { phmm_mappings_read_logp(self.0, per.as_mut_ptr(), &mut total) });
+        (total, per)
+    }
+    /// the same by the backward pass of that call, B.tables[0].mb (PHMMOutput::to_full_prob_backward, table.rs:492-494;
+    /// backward_by_forward or backward_with_mapping, backward.rs:59-142) -> (total, per read).  Mappings from
+    /// `generate_mappings` only.
+    pub fn read_logp_backward(&self, reads: &AmdReads) -> (f64, Vec<f64>) {
+        let (mut total, mut per) = (0f64, vec![0f64; reads.n_reads()]);
+        check(unsafe { phmm_mappings_read_logp_backward(self.0, per.as_mut_ptr(), &mut total) });
+        (total, per)
+    }
 }
 
 impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
@@ -207,6 +222,24 @@ impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
                                    &mut out, ptr::null_mut())
         });
         AmdMappings(out).into_mappings(reads)
+    }
+
+    /// `generate_mappings_amd_on` plus the forward and the backward ln P of every read from the same pass -- what
+    /// bin/mapping.rs:94-113 prints as pF / pB.  Their gap is the reference's check of a read (hmmv2/tests/dbg.rs:170-172):
+    /// the probability mass the truncated frontier lost.  -> (mappings, ln P forward, ln P backward)
+    pub fn generate_mappings_amd_with_probs(&self, reads: &AmdReads, mappings: Option<&Mappings>, use_max_ratio: bool)
+                                            -> (Mappings, Vec<f64>, Vec<f64>) {
+        let m = AmdModel::new(self);
+        let mp = mappings.map(|mp| AmdMappings::from_mappings(reads, mp));
+        let mut out = ptr::null_mut();
+        check(unsafe {
+            phmm_generate_mappings(m.0, reads.h, mp.as_ref().map_or(ptr::null(), |x| x.0 as *const _), use_max_ratio as c_int,
+                                   &mut out, ptr::null_mut())
+        });
+        let h = AmdMappings(out);
+        let (_, pf) = h.read_logp(reads);
+        let (_, pb) = h.read_logp_backward(reads);
+        (h.into_mappings(reads), pf, pb)
     }
 
     /// drop-in for `to_full_prob_sparse_backward` (freq.rs:153-163; backward_sparse per read, backward.rs:146-185)

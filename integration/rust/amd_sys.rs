@@ -102,6 +102,7 @@ extern "C" {
     pub fn phmm_mappings_export(mp: *const phmm_mappings, pos_off: *mut u64, nodes: *mut u32, logp: *mut f64) -> c_int;
     pub fn phmm_mappings_node_freqs(mp: *const phmm_mappings, n_nodes: u32, out_freq: *mut f64) -> c_int;
     pub fn phmm_mappings_read_logp(mp: *const phmm_mappings, out_logp: *mut f64, out_total: *mut f64) -> c_int;
+    pub fn phmm_mappings_read_logp_backward(mp: *const phmm_mappings, out_logp: *mut f64, out_total: *mut f64) -> c_int;
     pub fn phmm_mappings_destroy(mp: *mut phmm_mappings);
 
     pub fn phmm_full_prob_reads(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
