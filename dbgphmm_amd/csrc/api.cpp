@@ -743,4 +743,19 @@ int phmm_generate_mappings(phmm_model *m, const phmm_reads *reads, const phmm_ma
     });
 }
 
+int phmm_run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_lf,
+                                double *out_ef, double *out_if) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        check_mapping_nodes(m, mp, reads);
+        if (reads->R == 0) {
+            std::vector<double> z(std::max<size_t>(std::max(m->N, m->E), 1), 0.0);
+            put_doubles(out_ef, z.data(), m->E);
+            put_doubles(out_if, z.data(), m->N);
+            return;
+        }
+        run_with_mapping_edges(m, reads, mp, out_lf, out_ef, out_if);
+    });
+}
+
 }  // extern "C"

@@ -133,8 +133,141 @@ __device__ bool emit_mapping(const RecPool &mp, uint64_t pos_index, const uint32
     return true;
 }
 
+// ---- transition posteriors over the lists: the records of sparse_backward_kernel<CAP, true>
+// A wave appends NV candidate entries per lane to the record [base, base + cap) of a read position, zeros skipped, in
+// lane order and entry order inside a lane: the layout depends on the values alone.  Returns the new fill (uniform).
+static constexpr int EDGE_DEG = 8;  // node degree bound of the hinted path (full_prob_reads_hinted refuses more)
+template <int NV>
+__device__ __forceinline__ uint64_t rec_append(const SparseBwdEdgeArgs &a, uint64_t base, uint64_t fill, uint64_t cap,
+                                               const uint32_t (&key)[NV], const double (&val)[NV], uint32_t &err) {
+    int c = 0;
+#pragma unroll
+    for (int q = 0; q < NV; q++) c += val[q] != 0.0 ? 1 : 0;
+    const int incl = wave_iscan(c);
+    const uint64_t tot = (uint64_t)__builtin_amdgcn_readlane(incl, 63);
+    if (fill + tot > cap) {  // (cannot happen: the bound is exact; nothing is written past the record)
+        err |= SP_ERR_CAPACITY;
+        return fill;
+    }
+    uint64_t w = base + fill + (uint64_t)(incl - c);
+#pragma unroll
+    for (int q = 0; q < NV; q++)
+        if (val[q] != 0.0) {
+            a.rec_key[w] = key[q];
+            a.rec_val[w] = val[q];
+            w++;
+        }
+    return fill + tot;
+}
+
+// The edge terms of merged index i (freq.rs:349-365) for every edge k -> l with k in fr = F.table_merged(i), in the
+// form of edge_freq_kernel (dense.hip):
+//   to Match (i < len): t e_l(x[i]) B.table_merged(i+1).m[l] (p_MM F.m[k] + p_IM F.i[k] + p_DM F.d[k]) / P
+//   to Del:             t           B.table_merged(i).d[l]   (p_MD F.m[k] + p_ID F.i[k] + p_DD F.d[k]) / P
+// bm = prev (prev_init: b_init, m = p_end on EVERY node), bd = cur; i_is_len: B.table_merged(len) = b_init is the Del
+// target (d = p_end on every node) and there is no Match term.
 template <int CAP>
-__global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs a) {
+__device__ __forceinline__ uint64_t emit_edge_terms(const SparseBwdEdgeArgs &a, const FRec<CAP> &fr, const Col<CAP> &prev, bool prev_init,
+                                    const Col<CAP> &cur, bool i_is_len, uint8_t x, double logP, uint64_t base,
+                                    uint64_t fill, uint64_t cap, uint32_t &err) {
+    const SparseModel &M = a.M;
+    const LinParams &lp = M.lp;
+    const double wM = i_is_len ? 0.0 : exp((double)(fr.E + (prev_init ? 0 : prev.E)) * SP_LN2 - logP);
+    const double wD = exp((double)(fr.E + (i_is_len ? 0 : cur.E)) * SP_LN2 - logP);
+    const int n = fr.n;
+    for (int j0 = 0; j0 < n; j0 += 64) {
+        const int j = j0 + (int)threadIdx.x;
+        uint32_t key[EDGE_DEG];
+        double val[EDGE_DEG];
+#pragma unroll
+        for (int q = 0; q < EDGE_DEG; q++) {
+            key[q] = 0;
+            val[q] = 0.0;
+        }
+        if (j < n) {
+            const uint32_t k = fr.id[j];
+            const double fm = fr.m[j], fi = fr.i[j], fd = fr.d[j];
+            const double sm = lp.p_MM * fm + lp.p_IM * fi + lp.p_DM * fd;
+            const double sd = lp.p_MD * fm + lp.p_ID * fi + lp.p_DD * fd;
+            const uint32_t a0 = M.chi_off[k], deg = M.chi_off[k + 1] - a0;
+#pragma unroll
+            for (int q = 0; q < EDGE_DEG; q++) {
+                if ((uint32_t)q >= deg) break;
+                const double t = M.chi_w[a0 + q];
+                const uint32_t l = M.chi_node[a0 + q];
+                key[q] = M.chi_edge[a0 + q];
+                double term = 0.0;
+                if (!i_is_len) {
+                    double bm = lp.p_end;
+                    if (!prev_init) {
+                        const int ps = hash_find(prev, l);
+                        bm = ps >= 0 ? prev.m[ps] : 0.0;
+                    }
+                    // (a zero factor stays zero whatever the weight: no 0 * inf)
+                    const double v1 = sm * (M.emis[l] == x ? lp.p_match : lp.p_mismatch) * bm;
+                    if (v1 != 0.0) term += v1 * wM;
+                }
+                double bd = lp.p_end;
+                if (!i_is_len) {
+                    const int cs = hash_find(cur, l);
+                    bd = cs >= 0 ? cur.d[cs] : 0.0;
+                }
+                const double v2 = sd * bd;
+                if (v2 != 0.0) term += v2 * wD;
+                val[q] = t * term;
+            }
+        }
+        fill = rec_append<EDGE_DEG>(a, base, fill, cap, key, val, err);
+    }
+    return fill;
+}
+
+// The Begin terms of merged index i = pos < len (freq.rs:369-385) over the listed nodes, keys E + v:
+//   to Del:   c_D init_v B.tables[pos].d[v] / P               over cur
+//   to Match: c_M init_v e_v(x[pos]) B.tables[pos+1].m[v] / P  over prev (prev_init: dense, the host adds it)
+// with (c_M, c_D) = (p_MM, p_MD) at i = 0 (mb = 1) and ib_{i-1} (p_IM, p_ID) after; the InsBegin chain stays in the
+// exponent (exp(logib) alone is 0 from base ~105 on, and exp(-ln P) of a read with ln P < -709 is inf).
+template <int CAP>
+__device__ __forceinline__ uint64_t emit_begin_terms(const SparseBwdEdgeArgs &a, const Col<CAP> &prev, bool prev_init, const Col<CAP> &cur,
+                                     int pos, uint8_t x, double logP, uint64_t base, uint64_t fill, uint64_t cap,
+                                     uint32_t &err) {
+    const SparseModel &M = a.M;
+    const LinParams &lp = M.lp;
+    const double lib = pos == 0 ? 0.0 : M.logib[pos - 1];
+    const double cM = pos == 0 ? lp.p_MM : lp.p_IM, cD = pos == 0 ? lp.p_MD : lp.p_ID;
+    const double wD = exp(lib + (double)cur.E * SP_LN2 - logP);
+    for (int j0 = 0; j0 < cur.n; j0 += 64) {
+        const int j = j0 + (int)threadIdx.x;
+        uint32_t key[1] = {0};
+        double val[1] = {0.0};
+        if (j < cur.n) {
+            const uint32_t v = cur.id[j];
+            const double v2 = M.init[v] * cD * cur.d[j];
+            key[0] = a.E + v;
+            val[0] = v2 != 0.0 ? v2 * wD : 0.0;
+        }
+        fill = rec_append<1>(a, base, fill, cap, key, val, err);
+    }
+    if (!prev_init) {
+        const double wM = exp(lib + (double)prev.E * SP_LN2 - logP);
+        for (int j0 = 0; j0 < prev.n; j0 += 64) {
+            const int j = j0 + (int)threadIdx.x;
+            uint32_t key[1] = {0};
+            double val[1] = {0.0};
+            if (j < prev.n) {
+                const uint32_t v = prev.id[j];
+                const double v1 = M.init[v] * cM * (M.emis[v] == x ? lp.p_match : lp.p_mismatch) * prev.m[j];
+                key[0] = a.E + v;
+                val[0] = v1 != 0.0 ? v1 * wM : 0.0;
+            }
+            fill = rec_append<1>(a, base, fill, cap, key, val, err);
+        }
+    }
+    return fill;
+}
+
+template <int CAP, bool EDGES = false>
+__global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgsOf<EDGES> a) {
     __shared__ FRec<CAP> fr;
     __shared__ Col<CAP> cols[2];
     __shared__ double dA[CAP], dB[CAP];
@@ -161,12 +294,19 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
     double mb = 0.0;    // MatchBegin of the column computed last, same scale
     bool stopped = false;
     int stop_at = 0;
+    uint64_t end_fill = 0;  // (EDGES) entries of merged index len, at the head of the record of position len-1
     if (a.mode == 0) {
         pos = len - 1;
         // merged index len: F.tables[len-1] (.) b_init / P   (table.rs:414-434, backward.rs:197-211)
         if (!load_record<CAP>(a.fpool, p0 + (uint64_t)(len - 1), fr)) {
             stopped = true;  // does not fit this class (or missing): nothing done
             stop_at = len;
+        } else if constexpr (EDGES) {
+            // merged index len (Del into b_init only) opens the record of position len-1 (freq.rs:276-298)
+            const uint64_t rq = q0 + (uint64_t)(len - 1);
+            if (ok)
+                end_fill = emit_edge_terms<CAP>(a, fr, cols[0], true, cols[0], true, 0, logP, a.rec_off[rq], 0,
+                                                a.rec_off[rq + 1] - a.rec_off[rq], err);
         } else {
             const double w = ok ? exp((double)fr.E * SP_LN2 - logP) * lp.p_end : 0.0;
             for (int j = lane; j < fr.n; j += 64) val[j] = w * (fr.m[j] + fr.i[j] + fr.d[j]);
@@ -235,6 +375,20 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
         ib = bs.ib;
         mb = bs.mb;
         have_cols = 1;
+        if constexpr (EDGES) {
+            // merged index pos: fr = F.tables[pos-1], cur = B.tables[pos], prev = B.tables[pos+1] (b_init at len-1)
+            const uint64_t rq = q0 + (uint64_t)pos;
+            const uint64_t base = a.rec_off[rq], cap = a.rec_off[rq + 1] - base;
+            const uint8_t x = a.bases[((size_t)g * a.Lb + pos) * a.W + r];
+            uint64_t fill = pos == len - 1 ? end_fill : 0;
+            if (ok) {
+                if (pos > 0) fill = emit_edge_terms<CAP>(a, fr, prev, pos == len - 1, cur, false, x, logP, base, fill, cap, err);
+                fill = emit_begin_terms<CAP>(a, prev, pos == len - 1, cur, pos, x, logP, base, fill, cap, err);
+            }
+            if (lane == 0) a.rec_cnt[rq] = fill;
+            if (pos == 0) break;
+            continue;  // no mapping list
+        }
         if (pos == 0) break;  // (list mode) column 0 has no F.tables[-1]: nothing to emit
         // S = F.tables[pos-1] (.) B.tables[pos] / P over F's elements (table.rs:320-345, 500-505)
         const double w = ok ? exp((double)(fr.E + cur.E) * SP_LN2 - logP) : 0.0;
@@ -1501,24 +1655,13 @@ void mappings_map_nodes(phmm_model *m, const phmm_reads *reads, const phmm_mappi
     if (mp_in->read_logp_backward.size() != reads->R) (*out)->read_logp_backward.clear();
 }
 
-// PHMMModel::generate_mappings(reads, Some(mappings), use_max_ratio): run_with_mapping
-// (freq.rs:72-76) = forward_with_mapping (forward.rs:51-75) + backward_with_mapping
-// (backward.rs:59-93), then to_mapping_by_score_ratio / to_mapping(n_active) (hint.rs:124-142).
-void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, int use_max_ratio,
-                              phmm_mappings **out, double *out_node_freq) {
+// forward_with_mapping (forward.rs:51-75) of every read with one record per position, into the workspace pool `fp`,
+// and the arguments of the list pass that walks back over those records (sparse_backward_kernel, list mode): per-read
+// ln P in lf, the reads split into the 64- and 400-slot classes.  The caller sets what the pass emits.
+static void hinted_list_pass_setup(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in,
+                                   std::vector<double> &lf, SparseBwdArgs &ba, std::vector<uint32_t> (&cls)[2]) {
     hipStream_t s = current_stream();
     const uint64_t R = reads->R, n_pos = reads->total;
-    MappingSink sink{};
-    init_sink(m, reads, sink);
-    {   // every output list is a subset of its input list: the pool bound is exact
-        const uint64_t need = n_pos * 16 + mp_in->total_entries * 12 + (1u << 20);
-        if (need > sink.cap) {
-            sink.cap = need;
-            m->wset().aux[5].reserve(sink.cap);
-            sink.mp.base = m->wset().aux[5].as<uint8_t>();
-            sink.mp.cap = sink.cap;
-        }
-    }
     upload_reads(reads);
     upload_mappings(mp_in);
     // forward_with_mapping with one record per position
@@ -1531,11 +1674,11 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
     fp.base = fpool.as<uint8_t>();
     fp.top = fmeta.as<unsigned long long>();
     fp.off = (uint64_t *)(fmeta.as<char>() + 8);
-    std::vector<double> lf(R);
+    lf.assign(R, 0.0);
     double tot = 0.0;
     full_prob_reads_hinted(m, reads, mp_in, 1, nullptr, nullptr, lf.data(), &tot, &fp);
 
-    // backward_with_mapping + emit probs, one wave per read (W = 1 "lanes" = reads)
+    // backward_with_mapping, one wave per read (W = 1 "lanes" = reads)
     const int Lb = (int)reads->max_len;
     DevBuf &ctl = m->wset().aux[3];
     size_t cb = 0;
@@ -1561,7 +1704,7 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
     HIP_CHECK(hipMemcpyAsync(cp + o_len, hlen.data(), sizeof(int) * R, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(cp + o_logp, lf.data(), sizeof(double) * R, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(cp + o_bases, hb.data(), hb.size(), hipMemcpyHostToDevice, s));
-    SparseBwdArgs ba{};
+    ba = SparseBwdArgs{};
     ba.M = sparse_model_of(m);
     ba.d.N = (int)m->N;
     ba.d.len = (const int *)(cp + o_len);
@@ -1574,29 +1717,56 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
     ba.lane_pos0 = reads->d_off.as<uint64_t>();
     ba.map_pos0 = reads->d_off.as<uint64_t>();
     ba.lanes = (const uint32_t *)(cp + o_lanes);
-    ba.ratio_lin = std::exp(-m->params.active_node_max_ratio);
     ba.err = (uint32_t *)(cp + o_err);
     ba.list_off = mp_in->d_pos_off.as<uint64_t>();
     ba.list_nodes = mp_in->d_nodes.as<uint32_t>();
-    ba.topk = use_max_ratio ? 0 : (int)m->params.n_active_nodes;
     ba.mode = 0;
     ba.stop = (int *)(cp + o_stop);
     ba.hand = (BHandoff *)(cp + o_hand);
     ba.logb = (double *)(cp + o_logb);
-    std::vector<uint32_t> cls[2];
+    cls[0].clear();
+    cls[1].clear();
     for (uint64_t r = 0; r < R; r++) cls[mp_in->read_max_list[r] <= 64 ? 0 : 1].push_back((uint32_t)r);
+}
+
+// PHMMModel::generate_mappings(reads, Some(mappings), use_max_ratio): run_with_mapping
+// (freq.rs:72-76) = forward_with_mapping (forward.rs:51-75) + backward_with_mapping
+// (backward.rs:59-93), then to_mapping_by_score_ratio / to_mapping(n_active) (hint.rs:124-142).
+void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, int use_max_ratio,
+                              phmm_mappings **out, double *out_node_freq) {
+    hipStream_t s = current_stream();
+    const uint64_t R = reads->R, n_pos = reads->total;
+    MappingSink sink{};
+    init_sink(m, reads, sink);
+    {   // every output list is a subset of its input list: the pool bound is exact
+        const uint64_t need = n_pos * 16 + mp_in->total_entries * 12 + (1u << 20);
+        if (need > sink.cap) {
+            sink.cap = need;
+            m->wset().aux[5].reserve(sink.cap);
+            sink.mp.base = m->wset().aux[5].as<uint8_t>();
+            sink.mp.cap = sink.cap;
+        }
+    }
+    std::vector<double> lf;
+    SparseBwdArgs ba{};
+    std::vector<uint32_t> cls[2];
+    hinted_list_pass_setup(m, reads, mp_in, lf, ba, cls);
+    // the pass emits the mapping lists (emit probs of every position)
+    ba.ratio_lin = std::exp(-m->params.active_node_max_ratio);
+    ba.topk = use_max_ratio ? 0 : (int)m->params.n_active_nodes;
+    uint32_t *const d_lanes = const_cast<uint32_t *>(ba.lanes);
     for (int attempt = 0;; attempt++) {
         ba.mpool = sink.mp;
         for (int c = 0; c < 2; c++) {
             if (cls[c].empty()) continue;
-            HIP_CHECK(hipMemcpyAsync(cp + o_lanes, cls[c].data(), sizeof(uint32_t) * cls[c].size(), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(d_lanes, cls[c].data(), sizeof(uint32_t) * cls[c].size(), hipMemcpyHostToDevice, s));
             if (c == 0) hipLaunchKernelGGL((sparse_backward_kernel<64>), dim3((unsigned)cls[c].size()), dim3(64), 0, s, ba);
             else hipLaunchKernelGGL((sparse_backward_kernel<KMAX>), dim3((unsigned)cls[c].size()), dim3(64), 0, s, ba);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipStreamSynchronize(s));  // the lane list is reused by the next class
         }
         std::vector<uint32_t> herr(R);
-        HIP_CHECK(hipMemcpy(herr.data(), cp + o_err, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(herr.data(), ba.err, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
         bool pool_full = false;
         for (uint64_t r = 0; r < R; r++) {
             if (herr[r] & SP_ERR_POOL) pool_full = true;
@@ -1615,6 +1785,199 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
     std::vector<double> lb(R);
     HIP_CHECK(hipMemcpy(lb.data(), ba.logb, sizeof(double) * R, hipMemcpyDeviceToHost));
     finish_mappings(m, reads, sink, lf, lb, out, out_node_freq);
+}
+
+// ---------------------------------------------------------------- run_with_mapping + to_edge_and_init_freqs
+// Slots of the record of every read position p (sparse_backward_kernel<CAP, true>), an exact bound from the list sizes
+// nl() and the largest out-degree D: the edge terms of merged index p over F.tables[p-1] (p > 0), those of index len
+// over F.tables[len-1] (last position), the Begin terms over B.tables[p] and B.tables[p+1] (p + 1 < len).
+__global__ void __launch_bounds__(BLOCK) edge_rec_bound(const uint64_t *read_off, uint64_t R, const uint64_t *list_off,
+                                                        uint64_t n_pos, uint32_t D, uint64_t *out) {
+    const uint64_t p = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p > n_pos) return;
+    if (p == n_pos) {  // (the exclusive scan's total)
+        out[p] = 0;
+        return;
+    }
+    uint64_t lo = 0, hi = R;  // the read of p: last r with read_off[r] <= p
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (read_off[mid] <= p) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t p0 = read_off[lo], p1 = read_off[lo + 1];
+    auto nl = [&](uint64_t q) { return list_off[q + 1] - list_off[q]; };
+    uint64_t b = nl(p);
+    if (p + 1 < p1) b += nl(p + 1);
+    if (p > p0) b += (uint64_t)D * nl(p - 1);
+    if (p + 1 == p1) b += (uint64_t)D * nl(p);
+    out[p] = b;
+}
+// the records in position order, back to back (out_off: exclusive scan of the fills)
+__global__ void __launch_bounds__(BLOCK) edge_rec_compact(const uint64_t *rec_off, const uint64_t *rec_cnt,
+                                                          const uint64_t *out_off, uint64_t n_pos, const uint32_t *key,
+                                                          const double *val, uint32_t *okey, double *oval) {
+    const uint64_t p = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n_pos) return;
+    const uint64_t s = rec_off[p], n = rec_cnt[p], d = out_off[p];
+    for (uint64_t j = 0; j < n; j++) {
+        okey[d + j] = key[s + j];
+        oval[d + j] = val[s + j];
+    }
+}
+// The dense Begin terms of every read (b_init at both ends: m = d = p_end on every node), summed over the reads on the
+// host: init_v (A + sum_c T[c] e_v(c)) with c the reads' last bases.  Added after the per-key sums.
+__global__ void __launch_bounds__(BLOCK) init_end_terms(const double *init, const uint8_t *emis, uint32_t N, LinParams lp,
+                                                        double A, const uint8_t *letters, const double *T, int n_letters,
+                                                        double *freq) {
+    const uint32_t v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v >= N) return;
+    double mt = 0.0;
+    for (int c = 0; c < n_letters; c++) mt += T[c] * (emis[v] == letters[c] ? lp.p_match : lp.p_mismatch);
+    freq[v] += init[v] * (A + mt);
+}
+
+// PHMMModel::run_with_mapping (freq.rs:72-76) of every read on its lists, then PHMMOutput::to_edge_and_init_freqs
+// (freq.rs:276-298, 332-389) summed over the reads.  The list pass (sparse_backward_kernel<CAP, true>) holds at step pos
+// the three columns merged index pos reads: F.tables[pos-1], B.tables[pos] and B.tables[pos+1].  It writes the nonzero
+// terms of that index into the record of position pos (index len into that of len-1); the records are compacted in
+// position order, sorted by key (stable) and summed one wave per key, as Mappings::to_node_freqs: the same bits
+// whatever the timing.  The terms over b_init's every node come from two scalars per read.
+void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
+                            double *out_ef, double *out_if) {
+    hipStream_t s = current_stream();
+    const uint64_t R = reads->R, n_pos = reads->total;
+    const uint32_t N = m->N, E = m->E;
+    // The adaptive flow plans its memory as if every byte the pool holds were its own to reuse (planned_budget): the
+    // record slots and sort buffers of this call, gigabytes on a repeat, go back when it ends.
+    struct ReleaseScratch {
+        phmm_model *m;
+        ~ReleaseScratch() {
+            for (int i : {5, 6, 13, 14, 16, 17, 18, 19, 20, 21}) m->wset().aux[i].release();
+        }
+    } release_scratch{m};
+    std::vector<double> lf;
+    SparseBwdEdgeArgs ba{};
+    std::vector<uint32_t> cls[2];
+    hinted_list_pass_setup(m, reads, mp_in, lf, ba, cls);
+    ba.logb = nullptr;
+    ba.E = E;
+    // record bounds -> slot offsets
+    uint32_t D = 0;
+    for (uint32_t v = 0; v < N; v++) D = std::max(D, m->chi_off[v + 1] - m->chi_off[v]);
+    DevBuf &d_meta = m->wset().aux[6], &d_tmp = m->wset().aux[14];
+    const size_t meta_n = (size_t)(n_pos + 1);
+    d_meta.reserve(sizeof(uint64_t) * meta_n * 3);
+    uint64_t *rec_bound = d_meta.as<uint64_t>(), *rec_off = rec_bound + meta_n, *rec_cnt = rec_off + meta_n;
+    const unsigned nb = (unsigned)((n_pos + 1 + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(edge_rec_bound, dim3(nb), dim3(BLOCK), 0, s, reads->d_off.as<uint64_t>(), R, ba.list_off, n_pos, D,
+                       rec_bound);
+    size_t tb = 0;
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rec_bound, rec_off, (int)meta_n, s));
+    d_tmp.reserve(tb);
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, rec_bound, rec_off, (int)meta_n, s));
+    HIP_CHECK(hipMemsetAsync(rec_cnt, 0, sizeof(uint64_t) * meta_n, s));
+    uint64_t slots = 0;
+    HIP_CHECK(hipMemcpyAsync(&slots, rec_off + n_pos, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    DevBuf &d_key = m->wset().aux[5], &d_val = m->wset().aux[17];
+    d_key.reserve(sizeof(uint32_t) * std::max<uint64_t>(slots, 1));
+    d_val.reserve(sizeof(double) * std::max<uint64_t>(slots, 1));
+    ba.rec_off = rec_off;
+    ba.rec_key = d_key.as<uint32_t>();
+    ba.rec_val = d_val.as<double>();
+    ba.rec_cnt = rec_cnt;
+    uint32_t *const d_lanes = const_cast<uint32_t *>(ba.lanes);
+    for (int c = 0; c < 2; c++) {
+        if (cls[c].empty()) continue;
+        HIP_CHECK(hipMemcpyAsync(d_lanes, cls[c].data(), sizeof(uint32_t) * cls[c].size(), hipMemcpyHostToDevice, s));
+        if (c == 0) hipLaunchKernelGGL((sparse_backward_kernel<64, true>), dim3((unsigned)cls[c].size()), dim3(64), 0, s, ba);
+        else hipLaunchKernelGGL((sparse_backward_kernel<KMAX, true>), dim3((unsigned)cls[c].size()), dim3(64), 0, s, ba);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));  // the lane list is reused by the next class
+    }
+    {
+        std::vector<uint32_t> herr(R);
+        HIP_CHECK(hipMemcpy(herr.data(), ba.err, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+        for (uint64_t r = 0; r < R; r++)
+            if (herr[r]) PHMM_THROW(PHMM_EINTERNAL, "run_with_mapping edge pass error " + std::to_string(herr[r]) + " (read " +
+                                                        std::to_string(r) + ")");
+    }
+    trace("edge list pass");
+    // compaction in position order (the fills -> exclusive scan), stable sort by key, one wave per key
+    DevBuf &d_coff = m->wset().aux[13];
+    d_coff.reserve(sizeof(uint64_t) * meta_n);
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rec_cnt, d_coff.as<uint64_t>(), (int)meta_n, s));
+    d_tmp.reserve(tb);
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, rec_cnt, d_coff.as<uint64_t>(), (int)meta_n, s));
+    uint64_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, d_coff.as<uint64_t>() + n_pos, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t nt = std::max<uint64_t>(total, 1);
+    DevBuf &d_ck = m->wset().aux[18], &d_cv = m->wset().aux[19], &d_sk = m->wset().aux[20], &d_sv = m->wset().aux[21],
+           &d_freq = m->wset().aux[16];
+    d_ck.reserve(sizeof(uint32_t) * nt);
+    d_cv.reserve(sizeof(double) * nt);
+    d_sk.reserve(sizeof(uint32_t) * nt);
+    d_sv.reserve(sizeof(double) * nt);
+    const uint32_t K = E + N;
+    d_freq.reserve(sizeof(double) * K + 256 * (sizeof(double) + 1) + 256);
+    double *freq = d_freq.as<double>();
+    if (total) {
+        hipLaunchKernelGGL(edge_rec_compact, dim3((unsigned)((n_pos + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, rec_off,
+                           rec_cnt, d_coff.as<uint64_t>(), n_pos, ba.rec_key, ba.rec_val, d_ck.as<uint32_t>(),
+                           d_cv.as<double>());
+        int end_bit = 1;
+        while (end_bit < 32 && (1ull << end_bit) < K) end_bit++;
+        size_t sb = 0;
+        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, d_ck.as<uint32_t>(), d_sk.as<uint32_t>(), d_cv.as<double>(),
+                                                     d_sv.as<double>(), (int)total, 0, end_bit, s));
+        d_tmp.reserve(sb);
+        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, sb, d_ck.as<uint32_t>(), d_sk.as<uint32_t>(), d_cv.as<double>(),
+                                                     d_sv.as<double>(), (int)total, 0, end_bit, s));
+    }
+    hipLaunchKernelGGL(map_node_freq, dim3((K + NODE_FREQ_WAVES - 1) / NODE_FREQ_WAVES), dim3(64 * NODE_FREQ_WAVES), 0, s,
+                       d_sk.as<uint32_t>(), d_sv.as<double>(), total, K, freq);
+    HIP_CHECK(hipGetLastError());
+    // b_init's Begin terms (table.rs:414-434: B.table_merged(len) has m = d = p_end on every node):
+    //   index len-1, to Match: c_M(len-1) ib_{len-2} init_v e_v(x[len-1]) p_end / P  -> T[x[len-1]]
+    //   index len,   to Del:   p_ID ib_{len-1} init_v p_end / P                      -> A
+    // (c_M(0) = p_MM with mb = 1 for a read of one base, ib chain in the exponent as in the kernel)
+    {
+        std::vector<double> logib(std::max<uint64_t>(reads->max_len, 1));
+        HIP_CHECK(hipMemcpy(logib.data(), ba.M.logib, sizeof(double) * logib.size(), hipMemcpyDeviceToHost));
+        const LinParams &lp = m->lin;
+        double A = 0.0, T[256] = {0.0};
+        bool seen[256] = {false};
+        for (uint64_t r = 0; r < R; r++) {
+            const uint64_t len = reads->off[r + 1] - reads->off[r];
+            const uint8_t xl = reads->bases[reads->off[r + 1] - 1];
+            const double libM = len == 1 ? 0.0 : logib[len - 2];
+            const double cM = len == 1 ? lp.p_MM : lp.p_IM;
+            T[xl] += cM * lp.p_end * std::exp(libM - lf[r]);
+            seen[xl] = true;
+            A += lp.p_ID * lp.p_end * std::exp(logib[len - 1] - lf[r]);
+        }
+        std::vector<uint8_t> letters;
+        std::vector<double> tv;
+        for (int c = 0; c < 256; c++)
+            if (seen[c]) {
+                letters.push_back((uint8_t)c);
+                tv.push_back(T[c]);
+            }
+        double *d_T = freq + K;
+        uint8_t *d_letters = (uint8_t *)(d_T + 256);
+        HIP_CHECK(hipMemcpyAsync(d_T, tv.data(), sizeof(double) * tv.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_letters, letters.data(), letters.size(), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(init_end_terms, dim3((N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, ba.M.init, ba.M.emis, N, lp, A,
+                           (const uint8_t *)d_letters, (const double *)d_T, (int)letters.size(), freq + E);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));  // (host arrays above)
+    }
+    trace("edge freqs");
+    if (out_ef && E) copy_out(out_ef, freq, sizeof(double) * E);
+    if (out_if) copy_out(out_if, freq + E, sizeof(double) * N);
+    put_doubles(out_lf, lf.data(), R);
 }
 
 }  // namespace phmm

@@ -414,6 +414,9 @@ void mappings_map_nodes(phmm_model *m, const phmm_reads *reads, const phmm_mappi
                         const uint32_t *map_nodes, uint32_t n_old, phmm_mappings **out);
 void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, int use_max_ratio,
                               phmm_mappings **out, double *out_node_freq);
+// run_with_mapping + to_edge_and_init_freqs over the reads (mapping_flow.hip)
+void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
+                            double *out_ef, double *out_if);
 struct MappingSink;
 // by_ratio: use_max_ratio of forward_sparse (forward.rs:93-154); false = fixed warm-up + top n_active_nodes
 void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_logp, double *out_total,

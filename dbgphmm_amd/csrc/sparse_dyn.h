@@ -3,6 +3,7 @@
 #pragma once
 
 #include <mutex>
+#include <type_traits>
 
 #include "frontier_dev.h"
 
@@ -150,6 +151,18 @@ struct SparseBwdArgs {
     // mapping.nodes(0) after position 1, Begin sums only.  (Adaptive mode: the dense head has column 0.)
     double *logb;    // [lanes] or null
 };
+// The transition-posterior form of the list mode (sparse_backward_kernel<CAP, true>): instead of mapping lists, every
+// step emits the (key, value) terms of PHMMOutput::to_trans_and_init_probs at its merged index (freq.rs:332-389) into
+// the record of its read position.  Keys 0..E-1 are edges, E..E+N-1 Begin -> node.
+struct SparseBwdEdgeArgs : SparseBwdArgs {
+    uint32_t E;
+    const uint64_t *rec_off;  // [total_pos+1] first slot of each position's record (exact bound, edge_rec_bound)
+    uint32_t *rec_key;        // [rec_off[total_pos]]
+    double *rec_val;
+    uint64_t *rec_cnt;        // [total_pos] slots used
+};
+template <bool EDGES> using SparseBwdArgsOf = typename std::conditional<EDGES, SparseBwdEdgeArgs, SparseBwdArgs>::type;
+
 // stop[gi] on exit: s0      -> finished (column s0+1 handed to the dense kernel)
 //                   len     -> nothing done (the record of the last position does not fit the class)
 //                   other p -> positions > p are done, B.tables[p+1] is in the hand-off slot

@@ -276,6 +276,14 @@ class PHMMModel:
         _ffi.check(_ffi.lib().phmm_run_dense_edges(self._h, reads._h, _ptr(lf), _ptr(ef), _ptr(nf)))
         return lf, ef[:self.n_edges], nf
 
+    def run_with_mapping_edge_freqs(self, reads: ReadCollection, mappings: Mappings):
+        """PHMMModel::run_with_mapping (freq.rs:72-76) of every read on its lists, then
+        PHMMOutput::to_edge_and_init_freqs (freq.rs:276-298) summed over the reads
+        -> (per-read ln P, edge_freq[E], init_freq[N])."""
+        lf, ef, nf = np.empty(len(reads)), np.empty(max(self.n_edges, 1)), np.empty(self.n_nodes)
+        _ffi.check(_ffi.lib().phmm_run_with_mapping_edges(self._h, reads._h, mappings._h, _ptr(lf), _ptr(ef), _ptr(nf)))
+        return lf, ef[:self.n_edges], nf
+
     def q_score_exact(self, edge_freqs: np.ndarray, init_freqs: np.ndarray):
         """q_score_exact (src/hmmv2/q.rs:66-96) -> (init, trans, prior); QScore::total() is their sum."""
         ef = np.ascontiguousarray(edge_freqs, dtype=np.float64)

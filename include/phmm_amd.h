@@ -263,6 +263,17 @@ int phmm_generate_mappings(phmm_model *m, const phmm_reads *reads,
                            const phmm_mappings *mappings, int use_max_ratio,
                            phmm_mappings **out, double *out_node_freq);
 
+/* PHMMModel::run_with_mapping (freq.rs:72-76) of every read on its lists, then
+ * PHMMOutput::to_edge_and_init_freqs (freq.rs:276-298, 332-389), summed over the reads.
+ *   out_logp_forward[R]  per-read ln P of forward_with_mapping;
+ *   out_edge_freq[E], out_init_freq[N] as phmm_run_dense_edges defines them.
+ * Any output may be NULL or a device pointer.  The cost is that of phmm_generate_mappings with mappings: a list pass,
+ * no dense table.  Mappings of another read set are PHMM_EINVAL; so is a model under which a read has probability 0
+ * on its lists (as in phmm_generate_mappings with mappings).  Lists of at most 400 nodes, node degree at most 8.
+ * Repeated calls on the same inputs return the same bits. */
+int phmm_run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mappings,
+                                double *out_logp_forward, double *out_edge_freq, double *out_init_freq);
+
 /* ---- instrumentation ------------------------------------------------------------
  * Device time (ms, HIP events on the call's stream) and launch count of the dominant
  * kernel class in the most recent call of this thread, plus the algorithmic cell

@@ -276,6 +276,29 @@ impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
         check(unsafe { phmm_q_score_exact(m.0, ef.as_ptr(), nf.as_ptr(), q.as_mut_ptr()) });
         (q[0], q[1], q[2])
     }
+
+    /// run_with_mapping (freq.rs:72-76) of every read on its lists + to_edge_and_init_freqs (freq.rs:276-298), summed
+    /// over the reads -> (edge freqs, init freqs).  The cost of a hinted generate_mappings, no dense table.
+    pub fn to_edge_and_init_freqs_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings) -> (Vec<f64>, Vec<f64>) {
+        let m = AmdModel::new(self);
+        let mp = AmdMappings::from_mappings(reads, mappings);
+        let (mut ef, mut nf) = (vec![0f64; self.n_edges().max(1)], vec![0f64; self.n_nodes()]);
+        check(unsafe {
+            phmm_run_with_mapping_edges(m.0, reads.h, mp.0, ptr::null_mut(), ef.as_mut_ptr(), nf.as_mut_ptr())
+        });
+        ef.truncate(self.n_edges());
+        (ef, nf)
+    }
+
+    /// q_score_exact (q.rs:66-96) from the transition posteriors over the lists -> (init, trans, prior)
+    pub fn q_score_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings) -> (f64, f64, f64) {
+        let (ef, nf) = self.to_edge_and_init_freqs_with_mapping_amd(reads, mappings);
+        let m = AmdModel::new(self);
+        let mut q = [0f64; 3];
+        let ep = if ef.is_empty() { ptr::null() } else { ef.as_ptr() };
+        check(unsafe { phmm_q_score_exact(m.0, ep, nf.as_ptr(), q.as_mut_ptr()) });
+        (q[0], q[1], q[2])
+    }
 }
 
 /// The cut that pays (multi_dbg/posterior.rs:483-515): ONE call per sampler iteration for all candidate

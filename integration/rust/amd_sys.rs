@@ -124,6 +124,9 @@ extern "C" {
                                    out: *mut *mut phmm_mappings) -> c_int;
     pub fn phmm_generate_mappings(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
                                   use_max_ratio: c_int, out: *mut *mut phmm_mappings, out_node_freq: *mut f64) -> c_int;
+    pub fn phmm_run_with_mapping_edges(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                       out_logp_forward: *mut f64, out_edge_freq: *mut f64, out_init_freq: *mut f64)
+                                       -> c_int;
 
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
