@@ -83,6 +83,7 @@ def lib():
         "phmm_mappings_map_nodes": (i32, [vp, vp, vp, vp, vp, u32, vp]),
         "phmm_full_prob_reads_candidates": (i32, [vp, vp, vp, u32, vp, vp, vp, vp]),
         "phmm_full_prob_reads_copy_nums": (i32, [vp, vp, vp, u32, vp, u32, vp, vp]),
+        "phmm_full_prob_reads_copy_num_changes": (i32, [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "phmm_generate_mappings": (i32, [vp, vp, vp, i32, P(vp), vp]),
         "phmm_run_with_mapping_edges": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_last_call_stats": (i32, [i32, P(dbl), P(u64), P(u64)]),
@@ -105,7 +106,7 @@ DECLARED_SYMBOLS = [
     "phmm_mappings_total_positions", "phmm_mappings_total_entries", "phmm_mappings_export",
     "phmm_mappings_node_freqs", "phmm_mappings_read_logp", "phmm_mappings_read_logp_backward",
     "phmm_mappings_map_nodes", "phmm_mappings_destroy", "phmm_full_prob_reads",
-    "phmm_full_prob_reads_candidates", "phmm_full_prob_reads_copy_nums", "phmm_generate_mappings", "phmm_run_with_mapping_edges", "phmm_last_call_stats",
+    "phmm_full_prob_reads_candidates", "phmm_full_prob_reads_copy_nums", "phmm_full_prob_reads_copy_num_changes", "phmm_generate_mappings", "phmm_run_with_mapping_edges", "phmm_last_call_stats",
     "phmm_enable_timing",
 ]
 

@@ -206,17 +206,18 @@ void copy_out(void *dst, const void *src_dev, size_t bytes) {
     HIP_CHECK(hipStreamSynchronize(current_stream()));
 }
 
-void put_doubles(double *dst, const double *src, size_t n) {
+void put_bytes(void *dst, const void *src, size_t n) {
     if (!dst || !n) return;
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, dst) == hipSuccess && at.type == hipMemoryTypeDevice) {
-        HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, current_stream()));
+        HIP_CHECK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, current_stream()));
         HIP_CHECK(hipStreamSynchronize(current_stream()));
     } else {
         (void)hipGetLastError();
-        std::memcpy(dst, src, n * sizeof(double));
+        std::memcpy(dst, src, n);
     }
 }
+void put_doubles(double *dst, const double *src, size_t n) { put_bytes(dst, src, n * sizeof(double)); }
 
 // device-resident mappings -> host vectors (first host access only)
 void mappings_materialize_host(const phmm_mappings *cmp) {
@@ -710,6 +711,36 @@ int phmm_full_prob_reads_copy_nums(phmm_model *m, const phmm_reads *reads, const
         check_mapping_nodes(m, mp, reads);
         full_prob_reads_hinted(m, reads, mp, n_cand, nullptr, nullptr, out_logp, out_total, nullptr, copy_nums,
                                min_copy_num);
+    });
+}
+
+int phmm_full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp,
+                                          const uint32_t *base_copy_nums, uint32_t min_copy_num, uint32_t n_cand,
+                                          const uint64_t *change_off, const uint32_t *change_node,
+                                          const uint32_t *change_copy_num, double *out_logp, double *out_total,
+                                          uint64_t *out_n_rescored) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        if (!base_copy_nums) PHMM_THROW(PHMM_EINVAL, "NULL base copy numbers");
+        if (n_cand == 0) return;
+        if (!change_off) PHMM_THROW(PHMM_EINVAL, "NULL change_off");
+        if (change_off[0] != 0) PHMM_THROW(PHMM_EINVAL, "change_off[0] must be 0");
+        for (uint32_t c = 0; c < n_cand; c++)
+            if (change_off[c + 1] < change_off[c]) PHMM_THROW(PHMM_EINVAL, "change_off decreases");
+        if (change_off[n_cand] && (!change_node || !change_copy_num)) PHMM_THROW(PHMM_EINVAL, "NULL change arrays");
+        std::vector<uint32_t> seen(m->N, 0xffffffffu);  // candidate that last listed the node
+        for (uint32_t c = 0; c < n_cand; c++)
+            for (uint64_t j = change_off[c]; j < change_off[c + 1]; j++) {
+                const uint32_t v = change_node[j];
+                if (v >= m->N) PHMM_THROW(PHMM_EINVAL, "change node out of range");
+                if (seen[v] == c) PHMM_THROW(PHMM_EINVAL, "node listed twice in one candidate");
+                seen[v] = c;
+            }
+        check_mapping_nodes(m, mp, reads);
+        if (m->dev.max_degree > 8)
+            PHMM_THROW(PHMM_EINVAL, "sparse path supports node degree <= 8 (MultiDbg MAX_DEGREE is 5)");
+        full_prob_reads_copy_num_changes(m, reads, mp, base_copy_nums, min_copy_num, n_cand, change_off, change_node,
+                                         change_copy_num, out_logp, out_total, out_n_rescored);
     });
 }
 

@@ -408,6 +408,11 @@ void full_prob_reads_hinted(phmm_model *m, const phmm_reads *reads, const phmm_m
                             const double *init_logp, const double *trans_logp, double *out_logp,
                             double *out_total, const RecPool *pool = nullptr, const uint32_t *copy_nums = nullptr,
                             uint32_t min_copy_num = 0);
+// the same loop over candidates given as changes to a base copy-number vector, rescoring only the reads they touch
+void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp,
+                                      const uint32_t *base_cn, uint32_t min_cn, uint32_t n_cand, const uint64_t *chg_off,
+                                      const uint32_t *chg_node, const uint32_t *chg_cn, double *out_logp,
+                                      double *out_total, uint64_t *out_n_rescored);
 void upload_reads(const phmm_reads *r);
 void upload_mappings(const phmm_mappings *mp);
 void mappings_map_nodes(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, const uint32_t *map_off,
@@ -425,6 +430,7 @@ void generate_mappings_sparse(phmm_model *m, const phmm_reads *reads, phmm_mappi
                               bool by_ratio = true);
 void ensure_logib(phmm_model *m, size_t len);
 void put_doubles(double *dst, const double *src_host, size_t n);
+void put_bytes(void *dst, const void *src_host, size_t n);
 void dense_tables(phmm_model *m, const uint8_t *read, uint64_t len, double *f_m, double *f_i,
                   double *f_d, double *f_scal, double *b_m, double *b_i, double *b_d,
                   double *b_scal);

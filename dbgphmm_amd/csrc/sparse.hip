@@ -131,12 +131,13 @@ struct HStep {
     }
 };
 
+template <bool PAIRS = false>  // (PAIRS: as in hinted_score_kernel)
 __global__ void __launch_bounds__(64) hinted_lean_kernel(const HintedArgs a) {
     constexpr int CAP = 64;
     __shared__ HintedLeanShared sh;
     const int lane = threadIdx.x;
-    const uint32_t rd = a.read_ids[blockIdx.x];
-    const uint32_t cand = blockIdx.y;
+    const uint32_t rd = PAIRS ? a.read_ids[2 * blockIdx.x] : a.read_ids[blockIdx.x];
+    const uint32_t cand = PAIRS ? a.read_ids[2 * blockIdx.x + 1] : blockIdx.y;
     const double *init = a.init_c + (size_t)cand * a.M.N;
     const double *trans = a.trans_c + (size_t)cand * a.E;
     const ParRec *prec = a.M.prec;
@@ -378,7 +379,10 @@ template <int WG> __device__ __forceinline__ double group_sum(double v, int slot
     return __shfl(v, WG - 1, WG);
 }
 
-template <int WG, int CPL>
+// PAIRS (phmm_full_prob_reads_copy_num_changes): a wave takes its read and its G x CPL candidates from a work unit of
+// read_ids, {read, candidate of (group, c) at 1 + group * CPL + c}, 0xffffffff for an idle slot (which computes a
+// copy of the unit's first candidate and writes nothing), instead of a read and blockIdx.y.
+template <int WG, int CPL, bool PAIRS = false>
 __global__ void __launch_bounds__(64) hinted_packed_kernel(const HintedArgs a, const uint32_t n_cand) {
     // CPL candidates per lane on top of the G = 64 / WG candidate groups of a wave: the topology work of a position
     // (list, records, hash, lookups: ~100 VALU wave-instructions) is shared by G x CPL candidates, whose own work
@@ -387,15 +391,22 @@ __global__ void __launch_bounds__(64) hinted_packed_kernel(const HintedArgs a, c
     __shared__ HintedLeanShared sh;
     const int lane = threadIdx.x;
     const int slot = lane % WG, grp = lane / WG, gbase = grp * WG;
-    const uint32_t rd = a.read_ids[blockIdx.x];
+    const uint32_t *unit = a.read_ids + (size_t)blockIdx.x * (1 + G * CPL);
+    const uint32_t rd = PAIRS ? unit[0] : a.read_ids[blockIdx.x];
     uint32_t cand[CPL];
     bool cand_ok[CPL];
     const double *init[CPL], *trans[CPL];
 #pragma unroll
     for (int c = 0; c < CPL; c++) {
-        cand[c] = (blockIdx.y * G + (uint32_t)grp) * CPL + c;
-        cand_ok[c] = cand[c] < n_cand;
-        if (!cand_ok[c]) cand[c] = n_cand - 1;  // (idle slots of the last wave compute a copy; nothing is written)
+        if (PAIRS) {
+            cand[c] = unit[1 + grp * CPL + c];
+            cand_ok[c] = cand[c] != 0xffffffffu;
+            if (!cand_ok[c]) cand[c] = unit[1];
+        } else {
+            cand[c] = (blockIdx.y * G + (uint32_t)grp) * CPL + c;
+            cand_ok[c] = cand[c] < n_cand;
+            if (!cand_ok[c]) cand[c] = n_cand - 1;  // (idle slots of the last wave compute a copy; nothing is written)
+        }
         init[c] = a.init_c + (size_t)cand[c] * a.M.N;
         trans[c] = a.trans_c + (size_t)cand[c] * a.E;
     }
@@ -1026,7 +1037,7 @@ void full_prob_reads_hinted(phmm_model *m, const phmm_reads *reads, const phmm_m
         if (cls[c].empty()) continue;
         HIP_CHECK(hipMemcpyAsync(d_ids.p, cls[c].data(), cls[c].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         if (c == 0 && lean_ok) {
-            hipLaunchKernelGGL(hinted_lean_kernel, dim3((unsigned)cls[c].size(), n_cand), dim3(64), 0, s, a);
+            hipLaunchKernelGGL(hinted_lean_kernel<false>, dim3((unsigned)cls[c].size(), n_cand), dim3(64), 0, s, a);
         } else if (c == 0) launch_hinted<64, 2>(a, (uint32_t)cls[c].size(), n_cand);
         else if (c == 1) launch_hinted<128, 4>(a, (uint32_t)cls[c].size(), n_cand);
         else launch_hinted<400, 8>(a, (uint32_t)cls[c].size(), n_cand);
@@ -1100,6 +1111,370 @@ void full_prob_reads_hinted(phmm_model *m, const phmm_reads *reads, const phmm_m
     put_doubles(out_logp, h_out.data(), h_out.size());
     put_doubles(out_total, tot.data(), n_cand);
 }
+
+// ---------------------------------------------------------------- candidates as changes to a base vector
+// phmm_full_prob_reads_copy_num_changes: the loop of sample_posterior_once (posterior.rs:483-515) rescoring only the
+// reads a candidate touches.  With e(v) = max(cn(v), min_copy_num), T = sum of e over the emittable nodes, D_c the nodes
+// whose e differs from the base and A_c = D_c + parents(D_c): a read none of whose listed nodes is in A_c sees every
+// listed init scaled by T_base / T_c and every trans it uses unchanged (forward_with_mapping reads only those, and
+// every path takes exactly one init term), so ln P_c = ln P_base + ln(T_base / T_c).  DESIGN.md section 6.
+
+// bit c % 64 of word c / 64 in the mask of v and of every parent of v, per effective change {c, v}
+__global__ void __launch_bounds__(256) cnc_mark(const uint2 *chg, uint32_t n_chg, const uint32_t *par_off,
+                                                const uint32_t *par_node, uint32_t N, unsigned long long *node_mask) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_chg) return;
+    const uint32_t c = chg[j].x, v = chg[j].y;
+    const unsigned long long bit = 1ull << (c & 63);
+    unsigned long long *w = node_mask + (size_t)(c >> 6) * N;
+    atomicOr(&w[v], bit);
+    for (uint32_t q = par_off[v]; q < par_off[v + 1]; q++) atomicOr(&w[par_node[q]], bit);
+}
+// one wave per read: the OR of the mask words of every entry of its lists; word blockIdx.y
+__global__ void __launch_bounds__(256) cnc_read_mask(const uint64_t *read_off, uint64_t R, const uint64_t *map_pos_off,
+                                                     const uint32_t *map_nodes, uint32_t N,
+                                                     const unsigned long long *node_mask, unsigned long long *read_mask) {
+    const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const unsigned long long *w = node_mask + (size_t)blockIdx.y * N;
+    const uint64_t e0 = map_pos_off[read_off[r]], e1 = map_pos_off[read_off[r + 1]];
+    unsigned long long acc = 0;
+    for (uint64_t e = e0 + (threadIdx.x & 63); e < e1; e += 64) acc |= w[map_nodes[e]];
+    for (int off = 32; off >= 1; off >>= 1) acc |= __shfl_xor(acc, off);
+    if ((threadIdx.x & 63) == 0) read_mask[(size_t)blockIdx.y * R + r] = acc;
+}
+// copy-number vectors of the D candidates with a dirty read: the base, then their changes {slot, node, cn}
+__global__ void __launch_bounds__(256) cnc_expand(const uint32_t *base, uint32_t N, uint32_t *cn) {
+    const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+    if (v < N) cn[(size_t)blockIdx.y * N + v] = base[v];
+}
+__global__ void __launch_bounds__(256) cnc_apply(const uint3 *chg, uint32_t n_chg, uint32_t N, uint32_t *cn) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j < n_chg) cn[(size_t)chg[j].x * N + chg[j].y] = chg[j].z;
+}
+// results of the pairs {read, slot} out of the [D][R] planes the scoring kernels write
+__global__ void __launch_bounds__(256) cnc_gather(const uint2 *pairs, size_t n, uint64_t R, const double *out,
+                                                  const uint32_t *err, double *res, uint32_t *res_err) {
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const size_t k = (size_t)pairs[q].y * R + pairs[q].x;
+    res[q] = out[k];
+    res_err[q] = err[k];
+}
+
+void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp,
+                                      const uint32_t *base_cn, uint32_t min_cn, uint32_t C, const uint64_t *chg_off,
+                                      const uint32_t *chg_node, const uint32_t *chg_cn, double *out_logp,
+                                      double *out_total, uint64_t *out_n_rescored) {
+    hipStream_t s = current_stream();
+    const uint64_t R = reads->R;
+    const uint32_t N = m->N, E = m->E;
+    const uint8_t *emis = m->emission.data();
+    auto eff = [&](uint32_t k) { return std::max(k, min_cn); };
+    if (R == 0) {  // (an empty product: ln 1 per candidate, nothing rescored)
+        const std::vector<double> z(C, 0.0);
+        const std::vector<uint64_t> zn(C, 0);
+        put_doubles(out_total, z.data(), C);
+        put_bytes(out_n_rescored, zn.data(), (size_t)C * sizeof(uint64_t));
+        return;
+    }
+
+    // the base: one call of the full form
+    std::vector<double> base(R);
+    double base_tot = 0.0;
+    full_prob_reads_hinted(m, reads, mp, 1, nullptr, nullptr, base.data(), &base_tot, nullptr, base_cn, min_cn);
+
+    // effective changes (e differs from the base) and T_c, exact in integers
+    uint64_t Tb = 0;
+    for (uint32_t v = 0; v < N; v++)
+        if (emis[v] != (uint8_t)'n') Tb += eff(base_cn[v]);
+    std::vector<uint2> marks;  // {candidate, node}
+    std::vector<uint8_t> full(C, 0);
+    std::vector<double> shift(C, 0.0);
+    for (uint32_t c = 0; c < C; c++) {
+        int64_t dT = 0;
+        for (uint64_t j = chg_off[c]; j < chg_off[c + 1]; j++) {
+            const uint32_t v = chg_node[j];
+            const int64_t d = (int64_t)eff(chg_cn[j]) - (int64_t)eff(base_cn[v]);
+            if (d == 0) continue;
+            marks.push_back(make_uint2(c, v));
+            if (emis[v] != (uint8_t)'n') dT += d;
+        }
+        const uint64_t Tc = (uint64_t)((int64_t)Tb + dT);
+        full[c] = Tb == 0 || Tc == 0;  // (no finite shift: scored in full)
+        if (!full[c]) shift[c] = std::log((double)Tb / (double)Tc);
+    }
+
+    // read masks: bit c % 64 of word c / 64 set when the read's lists meet A_c
+    const uint32_t W = (C + 63) / 64;
+    std::vector<unsigned long long> rmask((size_t)W * R, 0ull);
+    DevBuf &d_mask = m->wset().aux[22], &d_list = m->wset().aux[23];
+    if (!marks.empty()) {
+        const size_t nm_bytes = (size_t)W * N * 8, rm_bytes = (size_t)W * R * 8;
+        d_mask.reserve(nm_bytes + rm_bytes);
+        d_list.reserve(marks.size() * sizeof(uint2));
+        unsigned long long *nm = d_mask.as<unsigned long long>(), *rm = nm + (size_t)W * N;
+        HIP_CHECK(hipMemsetAsync(nm, 0, nm_bytes, s));
+        HIP_CHECK(hipMemcpyAsync(d_list.p, marks.data(), marks.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(cnc_mark, dim3((unsigned)((marks.size() + 255) / 256)), dim3(256), 0, s, d_list.as<uint2>(),
+                           (uint32_t)marks.size(), m->dev.par_off.as<uint32_t>(), m->dev.par_node.as<uint32_t>(), N, nm);
+        hipLaunchKernelGGL(cnc_read_mask, dim3((unsigned)((R + 3) / 4), W), dim3(256), 0, s, reads->d_off.as<uint64_t>(), R,
+                           mp->d_pos_off.as<uint64_t>(), mp->d_nodes.as<uint32_t>(), N, nm, rm);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(rmask.data(), rm, rm_bytes, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+
+    // work list: (read, candidate) pairs, read-major, candidates ascending; slot = rank among the candidates with a pair
+    std::vector<unsigned long long> fullw(W, 0ull);
+    for (uint32_t c = 0; c < C; c++)
+        if (full[c]) fullw[c >> 6] |= 1ull << (c & 63);
+    std::vector<uint64_t> n_resc(C, 0);
+    std::vector<uint2> pairs;  // {read, candidate}, then {read, slot}
+    std::vector<uint64_t> read_pair_off(R + 1, 0);
+    for (uint64_t r = 0; r < R; r++) {
+        read_pair_off[r] = pairs.size();
+        if (reads->off[r + 1] == reads->off[r]) continue;
+        for (uint32_t w = 0; w < W; w++) {
+            unsigned long long b = rmask[(size_t)w * R + r] | fullw[w];
+            while (b) {
+                const uint32_t c = w * 64 + (uint32_t)__builtin_ctzll(b);
+                b &= b - 1;
+                pairs.push_back(make_uint2((uint32_t)r, c));
+                n_resc[c]++;
+            }
+        }
+    }
+    read_pair_off[R] = pairs.size();
+    std::vector<uint32_t> slot_of(C, 0xffffffffu), cand_of;
+    for (uint32_t c = 0; c < C; c++)
+        if (n_resc[c]) {
+            slot_of[c] = (uint32_t)cand_of.size();
+            cand_of.push_back(c);
+        }
+    const uint32_t D = (uint32_t)cand_of.size();
+    for (auto &q : pairs) q.y = slot_of[q.y];
+
+    std::vector<double> res(pairs.size());
+    EvTimer tm(timing_enabled());
+    if (D) {
+        // init / trans of the D dirty candidates: the base vector plus their changes, then the full form's cn_totals /
+        // cn_probs -- the same probabilities, bit for bit
+        DevBuf &cand_init = m->wset().aux[7], &cand_trans = m->wset().aux[8], &staging = m->wset().aux[9];
+        std::vector<uint3> apply;
+        for (uint32_t d = 0; d < D; d++)
+            for (uint64_t j = chg_off[cand_of[d]]; j < chg_off[cand_of[d] + 1]; j++)
+                apply.push_back(make_uint3(d, chg_node[j], chg_cn[j]));
+        const size_t ni = (size_t)D * N, ne = (size_t)D * E;
+        const size_t tot_at = (ni * sizeof(uint32_t) + 255) / 256 * 256;
+        staging.reserve(tot_at + D * sizeof(unsigned long long));
+        cand_init.reserve(ni * sizeof(double));
+        cand_trans.reserve(std::max<size_t>(ne, 1) * sizeof(double));
+        const size_t apply_at = ((size_t)N * sizeof(uint32_t) + 255) / 256 * 256;
+        d_list.reserve(apply_at + std::max<size_t>(apply.size(), 1) * sizeof(uint3));
+        uint32_t *d_base = d_list.as<uint32_t>();
+        uint3 *d_apply = (uint3 *)(d_list.as<char>() + apply_at);
+        uint32_t *d_cn = staging.as<uint32_t>();
+        unsigned long long *d_tot = (unsigned long long *)(staging.as<char>() + tot_at);
+        HIP_CHECK(hipMemcpyAsync(d_base, base_cn, N * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (!apply.empty())
+            HIP_CHECK(hipMemcpyAsync(d_apply, apply.data(), apply.size() * sizeof(uint3), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetAsync(d_tot, 0, D * sizeof(unsigned long long), s));
+        const unsigned nb = (unsigned)((N + 255) / 256);
+        hipLaunchKernelGGL(cnc_expand, dim3(nb, D), dim3(256), 0, s, (const uint32_t *)d_base, N, d_cn);
+        if (!apply.empty())
+            hipLaunchKernelGGL(cnc_apply, dim3((unsigned)((apply.size() + 255) / 256)), dim3(256), 0, s,
+                               (const uint3 *)d_apply, (uint32_t)apply.size(), N, d_cn);
+        hipLaunchKernelGGL(cn_totals, dim3(std::min(nb, 256u), D), dim3(256), 0, s, (const uint32_t *)d_cn,
+                           m->dev.emis.as<uint8_t>(), N, min_cn, d_tot);
+        hipLaunchKernelGGL(cn_probs, dim3(nb, D), dim3(256), 0, s, (const uint32_t *)d_cn, m->dev.emis.as<uint8_t>(),
+                           m->dev.chi_off.as<uint32_t>(), m->dev.chi_node.as<uint32_t>(), m->dev.chi_edge.as<uint32_t>(), N, E,
+                           min_cn, (const unsigned long long *)d_tot, cand_init.as<double>(), cand_trans.as<double>());
+        HIP_CHECK(hipGetLastError());
+
+        // the pairs, and the [D][R] result planes of the kernels
+        DevBuf &d_ids = m->wset().aux[10], &d_out = m->wset().aux[11], &d_err = m->wset().aux[12];
+        d_out.reserve((size_t)D * R * sizeof(double));
+        d_err.reserve((size_t)D * R * sizeof(uint32_t));
+        const size_t res_at = (pairs.size() * sizeof(uint2) + 255) / 256 * 256;
+        const size_t rerr_at = res_at + (pairs.size() * sizeof(double) + 255) / 256 * 256;
+        d_mask.reserve(rerr_at + pairs.size() * sizeof(uint32_t));  // (the masks are spent)
+        uint2 *d_pairs = d_mask.as<uint2>();
+        double *d_res = (double *)(d_mask.as<char>() + res_at);
+        uint32_t *d_rerr = (uint32_t *)(d_mask.as<char>() + rerr_at);
+        HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+        std::vector<uint32_t> rerr(pairs.size());
+        auto gather = [&](bool values) {
+            hipLaunchKernelGGL(cnc_gather, dim3((unsigned)((pairs.size() + 255) / 256)), dim3(256), 0, s,
+                               (const uint2 *)d_pairs, pairs.size(), R, (const double *)d_out.as<double>(),
+                               (const uint32_t *)d_err.as<uint32_t>(), d_res, d_rerr);
+            HIP_CHECK(hipGetLastError());
+            if (values) HIP_CHECK(hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(rerr.data(), d_rerr, rerr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+        };
+
+        HintedArgs a{};
+        a.M = sparse_model(m);
+        a.init_c = cand_init.as<double>();
+        a.trans_c = cand_trans.as<double>();
+        a.E = E;
+        a.bases = reads->d_bases.as<uint8_t>();
+        a.read_off = reads->d_off.as<uint64_t>();
+        a.map_pos_off = mp->d_pos_off.as<uint64_t>();
+        a.map_nodes = mp->d_nodes.as<uint32_t>();
+        a.R = R;
+        a.out_logp = d_out.as<double>();
+        a.err = d_err.as<uint32_t>();
+
+        // capacity classes by the longest list of each read, as full_prob_reads_hinted has them
+        const bool lean_ok = m->dev.max_degree <= (uint32_t)ADJ_DEG && !knobs().no_lean;
+        const bool packed_ok = C >= 2 && lean_ok && !knobs().no_packed;
+        std::vector<uint32_t> cls[3], pcls[3];
+        for (uint64_t r = 0; r < R; r++) {
+            if (read_pair_off[r + 1] == read_pair_off[r]) continue;
+            const uint32_t mx = mp->read_max_list[r];
+            if (packed_ok && mx <= 32) pcls[mx <= 8 ? 0 : (mx <= 16 ? 1 : 2)].push_back((uint32_t)r);
+            else cls[mx <= 64 ? 0 : (mx <= 128 ? 1 : 2)].push_back((uint32_t)r);
+        }
+        // packed classes: work units {read, G x CPL slots}, the three classes behind one upload
+        std::vector<uint32_t> units;
+        size_t unit_at[3], n_units[3];
+        int cpls[3];
+        for (int c = 0; c < 3; c++) {
+            const int G = c == 0 ? 8 : (c == 1 ? 4 : 2);
+            uint64_t np = 0;
+            for (uint32_t r : pcls[c]) np += read_pair_off[r + 1] - read_pair_off[r];
+            const int cpl_env = knobs().packed_cpl;
+            cpls[c] = cpl_env > 0 ? (cpl_env >= 2 ? 2 : 1) : (np >= (uint64_t)(2 * G) * pcls[c].size() ? 2 : 1);
+            const int pw = G * cpls[c];
+            unit_at[c] = units.size();
+            for (uint32_t r : pcls[c])
+                for (uint64_t q = read_pair_off[r]; q < read_pair_off[r + 1]; q += pw) {
+                    units.push_back(r);
+                    for (int k = 0; k < pw; k++) units.push_back(q + k < read_pair_off[r + 1] ? pairs[q + k].y : 0xffffffffu);
+                }
+            n_units[c] = (units.size() - unit_at[c]) / (size_t)(1 + pw);
+        }
+        if (!units.empty()) {
+            d_ids.reserve(units.size() * sizeof(uint32_t));
+            HIP_CHECK(hipMemcpyAsync(d_ids.p, units.data(), units.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            for (int c = 0; c < 3; c++) {
+                if (!n_units[c]) continue;
+                HintedArgs au = a;
+                au.read_ids = d_ids.as<uint32_t>() + unit_at[c];
+                const dim3 grid((unsigned)n_units[c]);
+                if (cpls[c] >= 2) {
+                    if (c == 0) hipLaunchKernelGGL((hinted_packed_kernel<8, 2, true>), grid, dim3(64), 0, s, au, D);
+                    else if (c == 1) hipLaunchKernelGGL((hinted_packed_kernel<16, 2, true>), grid, dim3(64), 0, s, au, D);
+                    else hipLaunchKernelGGL((hinted_packed_kernel<32, 2, true>), grid, dim3(64), 0, s, au, D);
+                } else {
+                    if (c == 0) hipLaunchKernelGGL((hinted_packed_kernel<8, 1, true>), grid, dim3(64), 0, s, au, D);
+                    else if (c == 1) hipLaunchKernelGGL((hinted_packed_kernel<16, 1, true>), grid, dim3(64), 0, s, au, D);
+                    else hipLaunchKernelGGL((hinted_packed_kernel<32, 1, true>), grid, dim3(64), 0, s, au, D);
+                }
+                HIP_CHECK(hipGetLastError());
+                stats().launches[2]++;
+            }
+            gather(false);
+            for (int c = 0; c < 3; c++)
+                for (uint32_t rd : pcls[c]) {
+                    uint32_t e = 0;
+                    for (uint64_t q = read_pair_off[rd]; q < read_pair_off[rd + 1]; q++) e |= rerr[q];
+                    if (!e) continue;
+                    if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
+                    cls[0].push_back(rd);
+                }
+        }
+        // one-candidate classes; a read any of whose pairs overflows a class is promoted.  The lean class takes one
+        // {read, slot} pair per wave.  The generic kernels (lists over 64 nodes, or degree above ADJ_DEG; few reads) run
+        // as in the full form, over the class's reads x the D candidates, and only the pairs are read back: a pair-list
+        // instantiation of hinted_score_kernel would change the register allocation of the shared fwd_list_step in the
+        // reads x candidates one, and a launch per candidate serialises long reads.
+        std::vector<uint32_t> wl;
+        for (int c = 0; c < 3; c++) {
+            if (cls[c].empty()) continue;
+            wl.clear();
+            if (c == 0 && lean_ok) {
+                for (uint32_t rd : cls[c])
+                    for (uint64_t q = read_pair_off[rd]; q < read_pair_off[rd + 1]; q++) {
+                        wl.push_back(pairs[q].x);
+                        wl.push_back(pairs[q].y);
+                    }
+                d_ids.reserve(wl.size() * sizeof(uint32_t));
+                HIP_CHECK(hipMemcpyAsync(d_ids.p, wl.data(), wl.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+                a.read_ids = d_ids.as<uint32_t>();
+                hipLaunchKernelGGL(hinted_lean_kernel<true>, dim3((unsigned)(wl.size() / 2)), dim3(64), 0, s, a);
+            } else {
+                d_ids.reserve(cls[c].size() * sizeof(uint32_t));
+                HIP_CHECK(hipMemcpyAsync(d_ids.p, cls[c].data(), cls[c].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+                a.read_ids = d_ids.as<uint32_t>();
+                if (c == 0) launch_hinted<64, 2>(a, (uint32_t)cls[c].size(), D);
+                else if (c == 1) launch_hinted<128, 4>(a, (uint32_t)cls[c].size(), D);
+                else launch_hinted<400, 8>(a, (uint32_t)cls[c].size(), D);
+            }
+            HIP_CHECK(hipGetLastError());
+            stats().launches[2]++;
+            gather(false);
+            for (uint32_t rd : cls[c]) {
+                uint32_t e = 0;
+                for (uint64_t q = read_pair_off[rd]; q < read_pair_off[rd + 1]; q++) e |= rerr[q];
+                if (!e) continue;
+                if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
+                if ((e & (SP_ERR_LINKS | SP_ERR_CAPACITY)) && c < 2) cls[c + 1].push_back(rd);
+                else PHMM_THROW(PHMM_ECAPACITY, "mapping list needs more than 400 slots / 8 in-list parents");
+            }
+        }
+        gather(true);
+        // pairs that came back -inf: the wide-range pass of full_prob_reads_hinted (short lists first)
+        if (!knobs().no_exact_hinted) {
+            std::vector<size_t> xq;
+            for (size_t q = 0; q < pairs.size(); q++)
+                if (res[q] == -INFINITY) xq.push_back(q);
+            if (!xq.empty()) {
+                std::stable_partition(xq.begin(), xq.end(), [&](size_t q) { return mp->read_max_list[pairs[q].x] <= 64; });
+                size_t n_small = 0;
+                while (n_small < xq.size() && mp->read_max_list[pairs[xq[n_small]].x] <= 64) n_small++;
+                std::vector<uint2> xs(xq.size());  // {slot, read}
+                for (size_t i = 0; i < xq.size(); i++) xs[i] = make_uint2(pairs[xq[i]].y, pairs[xq[i]].x);
+                const size_t xres_at = (xs.size() * sizeof(uint2) + 255) / 256 * 256;
+                d_ids.reserve(xres_at + xs.size() * sizeof(double));
+                uint2 *dp = d_ids.as<uint2>();
+                double *dres = (double *)(d_ids.as<char>() + xres_at);
+                HIP_CHECK(hipMemcpyAsync(dp, xs.data(), xs.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+                if (n_small)
+                    hipLaunchKernelGGL((hinted_exact_kernel<64, 256>), dim3((unsigned)n_small), dim3(64), 0, s, a,
+                                       (const uint2 *)dp, dres);
+                if (n_small < xs.size())
+                    hipLaunchKernelGGL((hinted_exact_kernel<PHMM_MAX_ACTIVE_NODES, 1024>), dim3((unsigned)(xs.size() - n_small)),
+                                       dim3(64), 0, s, a, (const uint2 *)(dp + n_small), dres + n_small);
+                HIP_CHECK(hipGetLastError());
+                std::vector<double> hres(xs.size());
+                HIP_CHECK(hipMemcpyAsync(hres.data(), dres, hres.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+                for (size_t i = 0; i < xq.size(); i++)
+                    if (hres[i] == hres[i]) res[xq[i]] = hres[i];
+                stats().launches[2]++;
+            }
+        }
+    }
+    stats().ms[2] += tm.stop();  // (on top of the base pass; cells stay those of the base pass)
+
+    // clean reads: base + ln(T_base / T_c); the rescored pairs over them; totals in read order, as the full form sums
+    std::vector<double> out((size_t)C * R);
+    std::vector<double> tot(C, 0.0);
+    for (uint32_t c = 0; c < C; c++) {
+        double *o = out.data() + (size_t)c * R;
+        for (uint64_t r = 0; r < R; r++) o[r] = (full[c] || reads->off[r + 1] == reads->off[r]) ? base[r] : base[r] + shift[c];
+    }
+    for (size_t q = 0; q < pairs.size(); q++) out[(size_t)cand_of[pairs[q].y] * R + pairs[q].x] = res[q];
+    for (uint32_t c = 0; c < C; c++)
+        for (uint64_t r = 0; r < R; r++) tot[c] += out[(size_t)c * R + r];
+    put_doubles(out_logp, out.data(), out.size());
+    put_doubles(out_total, tot.data(), C);
+    put_bytes(out_n_rescored, n_resc.data(), (size_t)C * sizeof(uint64_t));
+}
+
 
 }  // namespace phmm
 

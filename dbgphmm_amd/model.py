@@ -307,6 +307,27 @@ class PHMMModel:
                                                              int(min_copy_num), _ptr(lp), _ptr(tot)))
         return tot, lp
 
+    def to_full_prob_reads_copy_num_changes(self, reads: ReadCollection, mappings: Mappings, base: np.ndarray,
+                                            changes, min_copy_num: int = 0, out_logp=None):
+        """The loop of sample_posterior_once (posterior.rs:483-515) with each candidate given as changes to the base
+        copy-number vector: changes = (off[C+1], node, cn), candidate c = base with cn[node[j]] = cn[j] for j in
+        [off[c], off[c+1]) (see copy_num_changes).  Only the reads whose lists meet a changed node or one of its
+        parents are run again; the others get ln P_base + ln(T_base / T_c).  Same values as
+        to_full_prob_reads_copy_nums on the materialised vectors -> (totals[C], per_read[C,R], n_rescored[C])."""
+        b = np.ascontiguousarray(base, dtype=np.uint32)
+        off, node, cn = changes
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        node = np.ascontiguousarray(node, dtype=np.uint32)
+        cn = np.ascontiguousarray(cn, dtype=np.uint32)
+        Cn = off.size - 1
+        lp = np.empty((Cn, len(reads))) if out_logp is None else out_logp
+        tot = np.empty(Cn)
+        nr = np.empty(Cn, dtype=np.uint64)
+        _ffi.check(_ffi.lib().phmm_full_prob_reads_copy_num_changes(
+            self._h, reads._h, mappings._h if mappings else None, _ptr(b), int(min_copy_num), Cn, _ptr(off),
+            _ptr(node), _ptr(cn), _ptr(lp), _ptr(tot), _ptr(nr)))
+        return tot, lp, nr
+
     def generate_mappings(self, reads: ReadCollection, mappings: Optional[Mappings] = None,
                           use_max_ratio: bool = True, out_node_freq=None):
         """PHMMModel::generate_mappings (hint.rs:193-220) -> (Mappings, node_freq[N])."""
@@ -315,6 +336,17 @@ class PHMMModel:
         _ffi.check(_ffi.lib().phmm_generate_mappings(self._h, reads._h, mappings._h if mappings else None,
                                                      int(use_max_ratio), C.byref(h), _ptr(nf)))
         return Mappings(h, reads), nf
+
+
+def copy_num_changes(base: np.ndarray, candidates: np.ndarray):
+    """Candidates [C,N] as changes to the base copy-number vector [N] -> CSR (off[C+1] uint64, node uint32,
+    cn uint32): the nodes where candidate c differs from the base, ascending, with their new copy numbers."""
+    b = np.asarray(base, dtype=np.uint32).reshape(-1)
+    cands = np.asarray(candidates, dtype=np.uint32).reshape(-1, b.size)
+    ci, node = np.nonzero(cands != b[None, :])
+    off = np.zeros(cands.shape[0] + 1, dtype=np.uint64)
+    np.cumsum(np.bincount(ci, minlength=cands.shape[0]), out=off[1:])
+    return off, node.astype(np.uint32), cands[ci, node].astype(np.uint32)
 
 
 class PHMMOutput:

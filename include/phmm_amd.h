@@ -217,6 +217,23 @@ int phmm_full_prob_reads_copy_nums(phmm_model *m, const phmm_reads *reads,
                                    const uint32_t *copy_nums, uint32_t min_copy_num,
                                    double *out_logp, double *out_total);
 
+/* The same loop with each candidate given as changes to a base copy-number vector, rescoring only the reads it
+ * touches.  Candidate c = base_copy_nums[N] with cn[change_node[j]] = change_copy_num[j] (absolute new values) for
+ * j in [change_off[c], change_off[c+1]); change_off has n_candidates + 1 entries.  All inputs are host pointers.
+ * With e(v) = max(cn[v], min_copy_num), T = sum of e over the emittable nodes, D_c = the nodes whose e differs from the
+ * base and A_c = D_c plus their parents: a read none of whose listed nodes is in A_c gets ln P_base + ln(T_base / T_c)
+ * (exact in real arithmetic: every init it reads is scaled by T_base / T_c and no trans it uses changes); the others
+ * are run through the kernels.  A candidate with T_c = 0, or every candidate when T_base = 0, is scored in full.
+ *   out_logp [C][R], out_total [C]: as phmm_full_prob_reads_copy_nums on the materialised vectors (rescored reads
+ *   bit-equal to it, the others within rounding);  out_n_rescored [C]: non-empty reads run through the kernels.
+ * Any output may be NULL or a device pointer.  NULL mappings or base, mappings of another read set, change_off not
+ * starting at 0 or decreasing, a node id >= N, a node listed twice within one candidate and node degree > 8 are
+ * PHMM_EINVAL, with nothing written; n_candidates = 0 writes nothing.  Repeated calls return the same bits. */
+int phmm_full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads,
+        const phmm_mappings *mappings, const uint32_t *base_copy_nums, uint32_t min_copy_num,
+        uint32_t n_candidates, const uint64_t *change_off, const uint32_t *change_node,
+        const uint32_t *change_copy_num, double *out_logp, double *out_total, uint64_t *out_n_rescored);
+
 /* PHMMModel::to_full_prob_sparse_backward (freq.rs:153-163): ln P(read) from PHMMModel::backward_sparse
  * (backward.rs:146-185) -- dense b_step over the last n_warmup positions, then the backward recursion on
  * its own frontier: top_nodes(n_active_nodes) of the previous column, adaptive b_step (backward.rs:216-261).

@@ -331,4 +331,20 @@ impl AmdLikelihood {
         });
         totals.into_iter().map(Prob::from_log_prob).collect()
     }
+    /// The same for candidates given as changes to `base` (n_nodes copy numbers): candidate c sets
+    /// node[j] to cn[j] for j in off[c]..off[c+1].  Only the reads a candidate touches are run again
+    /// (phmm_full_prob_reads_copy_num_changes) -> (ln P(R | X_c), reads rescored) per candidate.
+    pub fn likelihoods_of_changes(&mut self, base: &[u32], off: &[u64], node: &[u32], cn: &[u32],
+                                  min_copy_num: u32) -> (Vec<Prob>, Vec<u64>) {
+        assert!(base.len() == self.n_nodes && !off.is_empty() && node.len() == cn.len());
+        let c = off.len() - 1;
+        let mut totals = vec![0f64; c];
+        let mut rescored = vec![0u64; c];
+        check(unsafe {
+            phmm_full_prob_reads_copy_num_changes(self.model.0, self.reads.h, self.mappings.0, base.as_ptr(),
+                                                  min_copy_num, c as u32, off.as_ptr(), node.as_ptr(), cn.as_ptr(),
+                                                  ptr::null_mut(), totals.as_mut_ptr(), rescored.as_mut_ptr())
+        });
+        (totals.into_iter().map(Prob::from_log_prob).collect(), rescored)
+    }
 }

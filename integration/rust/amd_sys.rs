@@ -113,6 +113,12 @@ extern "C" {
     pub fn phmm_full_prob_reads_copy_nums(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
                                           n_candidates: u32, copy_nums: *const u32, min_copy_num: u32,
                                           out_logp: *mut f64, out_total: *mut f64) -> c_int;
+    pub fn phmm_full_prob_reads_copy_num_changes(m: *mut phmm_model, reads: *const phmm_reads,
+                                                 mappings: *const phmm_mappings, base_copy_nums: *const u32,
+                                                 min_copy_num: u32, n_candidates: u32, change_off: *const u64,
+                                                 change_node: *const u32, change_copy_num: *const u32,
+                                                 out_logp: *mut f64, out_total: *mut f64,
+                                                 out_n_rescored: *mut u64) -> c_int;
     pub fn phmm_full_prob_sparse_backward(m: *mut phmm_model, reads: *const phmm_reads, out_logp: *mut f64,
                                           out_total: *mut f64) -> c_int;
     pub fn phmm_run_sparse(m: *mut phmm_model, reads: *const phmm_reads, out_logp_forward: *mut f64,
