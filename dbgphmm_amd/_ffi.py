@@ -84,6 +84,12 @@ def lib():
         "phmm_full_prob_reads_candidates": (i32, [vp, vp, vp, u32, vp, vp, vp, vp]),
         "phmm_full_prob_reads_copy_nums": (i32, [vp, vp, vp, u32, vp, u32, vp, vp]),
         "phmm_full_prob_reads_copy_num_changes": (i32, [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "phmm_likelihood_create": (i32, [vp, vp, vp, vp, u32, P(vp)]),
+        "phmm_likelihood_score_changes": (i32, [vp, u32, vp, vp, vp, vp, vp, vp]),
+        "phmm_likelihood_move": (i32, [vp, u64, vp, vp, vp, vp]),
+        "phmm_likelihood_current": (i32, [vp, vp, vp, vp]),
+        "phmm_likelihood_refresh": (i32, [vp]),
+        "phmm_likelihood_destroy": (None, [vp]),
         "phmm_generate_mappings": (i32, [vp, vp, vp, i32, P(vp), vp]),
         "phmm_run_with_mapping_edges": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_last_call_stats": (i32, [i32, P(dbl), P(u64), P(u64)]),
@@ -108,6 +114,8 @@ DECLARED_SYMBOLS = [
     "phmm_mappings_map_nodes", "phmm_mappings_destroy", "phmm_full_prob_reads",
     "phmm_full_prob_reads_candidates", "phmm_full_prob_reads_copy_nums", "phmm_full_prob_reads_copy_num_changes", "phmm_generate_mappings", "phmm_run_with_mapping_edges", "phmm_last_call_stats",
     "phmm_enable_timing",
+    "phmm_likelihood_create", "phmm_likelihood_score_changes", "phmm_likelihood_move", "phmm_likelihood_current",
+    "phmm_likelihood_refresh", "phmm_likelihood_destroy",
 ]
 
 

@@ -744,6 +744,91 @@ int phmm_full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads
     });
 }
 
+// ---- phmm_likelihood: the checks of the change form, then sparse.hip
+// a change list names no node >= N and no node twice (stamps: O(changes) per call, not O(N))
+static void check_change_list(phmm_likelihood *lk, uint64_t j0, uint64_t j1, const uint32_t *node) {
+    if (++lk->stamp == 0) {
+        std::fill(lk->seen.begin(), lk->seen.end(), 0u);
+        lk->stamp = 1;
+    }
+    for (uint64_t j = j0; j < j1; j++) {
+        const uint32_t v = node[j];
+        if (v >= lk->m->N) PHMM_THROW(PHMM_EINVAL, "change node out of range");
+        if (lk->seen[v] == lk->stamp) PHMM_THROW(PHMM_EINVAL, "node listed twice in one change list");
+        lk->seen[v] = lk->stamp;
+    }
+}
+
+int phmm_likelihood_create(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, const uint32_t *copy_nums,
+                           uint32_t min_copy_num, phmm_likelihood **out) {
+    if (!out) return fail(PHMM_EINVAL, "out is NULL");
+    *out = nullptr;
+    phmm_likelihood *lk = nullptr;
+    const int rc = guarded_on(m, [&] {
+        if (!reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL reads or mappings");
+        if (!copy_nums) PHMM_THROW(PHMM_EINVAL, "NULL copy numbers");
+        check_mapping_nodes(m, mp, reads);
+        if (m->dev.max_degree > 8)
+            PHMM_THROW(PHMM_EINVAL, "sparse path supports node degree <= 8 (MultiDbg MAX_DEGREE is 5)");
+        lk = new phmm_likelihood();
+        lk->m = m;
+        lk->reads = reads;
+        lk->mp = mp;
+        lk->min_cn = min_copy_num;
+        lk->cn.assign(copy_nums, copy_nums + m->N);
+        lk->seen.assign(m->N, 0u);
+        lk->d_cn.upload(lk->cn.data(), (size_t)m->N * sizeof(uint32_t));
+        lk->d_val.reserve(std::max<size_t>(reads->R, 1) * sizeof(double));
+        lk->d_tat.reserve(std::max<size_t>(reads->R, 1) * sizeof(unsigned long long));
+        likelihood_refresh(lk);
+    });
+    if (rc != PHMM_OK) {
+        delete lk;
+        return rc;
+    }
+    *out = lk;
+    return PHMM_OK;
+}
+
+int phmm_likelihood_score_changes(phmm_likelihood *lk, uint32_t n_cand, const uint64_t *change_off,
+                                  const uint32_t *change_node, const uint32_t *change_copy_num, double *out_logp,
+                                  double *out_total, uint64_t *out_n_rescored) {
+    if (!lk) return fail(PHMM_EINVAL, "NULL likelihood handle");
+    return guarded_on(lk->m, [&] {
+        if (n_cand == 0) return;
+        if (!change_off) PHMM_THROW(PHMM_EINVAL, "NULL change_off");
+        if (change_off[0] != 0) PHMM_THROW(PHMM_EINVAL, "change_off[0] must be 0");
+        for (uint32_t c = 0; c < n_cand; c++)
+            if (change_off[c + 1] < change_off[c]) PHMM_THROW(PHMM_EINVAL, "change_off decreases");
+        if (change_off[n_cand] && (!change_node || !change_copy_num)) PHMM_THROW(PHMM_EINVAL, "NULL change arrays");
+        for (uint32_t c = 0; c < n_cand; c++) check_change_list(lk, change_off[c], change_off[c + 1], change_node);
+        likelihood_score_changes(lk, n_cand, change_off, change_node, change_copy_num, out_logp, out_total,
+                                 out_n_rescored);
+    });
+}
+
+int phmm_likelihood_move(phmm_likelihood *lk, uint64_t n_changes, const uint32_t *change_node,
+                         const uint32_t *change_copy_num, double *out_total, uint64_t *out_n_rescored) {
+    if (!lk) return fail(PHMM_EINVAL, "NULL likelihood handle");
+    return guarded_on(lk->m, [&] {
+        if (n_changes && (!change_node || !change_copy_num)) PHMM_THROW(PHMM_EINVAL, "NULL change arrays");
+        check_change_list(lk, 0, n_changes, change_node);
+        likelihood_move(lk, n_changes, change_node, change_copy_num, out_total, out_n_rescored);
+    });
+}
+
+int phmm_likelihood_current(const phmm_likelihood *lk, uint32_t *out_copy_nums, double *out_logp, double *out_total) {
+    if (!lk) return fail(PHMM_EINVAL, "NULL likelihood handle");
+    return guarded_on(lk->m, [&] { likelihood_current(lk, out_copy_nums, out_logp, out_total); });
+}
+
+int phmm_likelihood_refresh(phmm_likelihood *lk) {
+    if (!lk) return fail(PHMM_EINVAL, "NULL likelihood handle");
+    return guarded_on(lk->m, [&] { likelihood_refresh(lk); });
+}
+
+void phmm_likelihood_destroy(phmm_likelihood *lk) { delete lk; }
+
 int phmm_mappings_map_nodes(phmm_model *model_after, const phmm_reads *reads, const phmm_mappings *mp,
                             const uint32_t *map_off, const uint32_t *map_nodes, uint32_t n_nodes_before,
                             phmm_mappings **out) {

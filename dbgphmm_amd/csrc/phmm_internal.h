@@ -317,6 +317,23 @@ namespace phmm {
 void mappings_materialize_host(const phmm_mappings *mp);
 }
 
+// The sampler's state at one k (MultiDbg::to_likelihood, posterior.rs:247-255, through the greedy search of
+// sample_posterior, posterior.rs:314-417): the current copy-number vector and every read's ln P under it, on the device.
+// The value of read r under the current vector is val[r] + ln(T_at[r] / T): val[r] is what the kernels gave when r was
+// last rescored and T_at[r] the (integer) T of that moment, so a read no move touches is rounded once however many
+// moves lie between.  The arrays belong to the handle, not to the device workspace.
+struct phmm_likelihood {
+    phmm_model *m = nullptr;            // borrowed, as reads and mappings: they outlive the handle
+    const phmm_reads *reads = nullptr;
+    const phmm_mappings *mp = nullptr;
+    uint32_t min_cn = 0;
+    uint64_t T = 0;                     // sum of max(cn, min_cn) over the emittable nodes
+    std::vector<uint32_t> cn;           // host mirror of d_cn (the O(changes) integer work reads it)
+    phmm::DevBuf d_cn, d_val, d_tat;    // u32[N], f64[R], u64[R]
+    std::vector<uint32_t> seen;         // [N] stamp of the change list that last named the node
+    uint32_t stamp = 0;
+};
+
 namespace phmm {
 
 struct CallStats {
@@ -413,6 +430,13 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
                                       const uint32_t *base_cn, uint32_t min_cn, uint32_t n_cand, const uint64_t *chg_off,
                                       const uint32_t *chg_node, const uint32_t *chg_cn, double *out_logp,
                                       double *out_total, uint64_t *out_n_rescored);
+// phmm_likelihood (sparse.hip): the same scoring against a vector and per-read values kept on the device
+void likelihood_refresh(phmm_likelihood *lk);  // also the first scoring of phmm_likelihood_create
+void likelihood_score_changes(phmm_likelihood *lk, uint32_t n_cand, const uint64_t *chg_off, const uint32_t *chg_node,
+                              const uint32_t *chg_cn, double *out_logp, double *out_total, uint64_t *out_n_rescored);
+void likelihood_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_node, const uint32_t *chg_cn,
+                     double *out_total, uint64_t *out_n_rescored);
+void likelihood_current(const phmm_likelihood *lk, uint32_t *out_cn, double *out_logp, double *out_total);
 void upload_reads(const phmm_reads *r);
 void upload_mappings(const phmm_mappings *mp);
 void mappings_map_nodes(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, const uint32_t *map_off,

@@ -1162,35 +1162,58 @@ __global__ void __launch_bounds__(256) cnc_gather(const uint2 *pairs, size_t n, 
     res_err[q] = err[k];
 }
 
-void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp,
-                                      const uint32_t *base_cn, uint32_t min_cn, uint32_t C, const uint64_t *chg_off,
-                                      const uint32_t *chg_node, const uint32_t *chg_cn, double *out_logp,
-                                      double *out_total, uint64_t *out_n_rescored) {
+// results of the exact pass over the pairs {slot, read} back into the [D][R] planes (NaN: the plane's value stands)
+__global__ void __launch_bounds__(256) cnc_scatter(const uint2 *pairs, const double *res, size_t n, uint64_t R,
+                                                   double *out) {
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const double v = res[q];
+    if (v == v) out[(size_t)pairs[q].x * R + pairs[q].y] = v;
+}
+
+namespace {
+
+// One batch of candidates against a base vector: which (read, candidate) pairs are rescored, and their values.
+// The stateless entry point composes its outputs from this on the host (its bits are pinned by its tests); a
+// phmm_likelihood handle brings the base vector on the device and composes on the device.
+struct CncJob {
+    // in
+    const uint32_t *base_cn = nullptr;  // host [N]
+    const uint32_t *d_base = nullptr;   // the same vector on the device; nullptr: uploaded from base_cn
+    uint64_t Tb = 0;                    // sum of e(base) over the emittable nodes
+    uint32_t min_cn = 0, C = 0;
+    const uint64_t *chg_off = nullptr;
+    const uint32_t *chg_node = nullptr, *chg_cn = nullptr;
+    bool on_device = false;  // keep the read masks (aux[13]) and every final value in the [D][R] planes (aux[11])
+    // out
+    std::vector<uint8_t> full;       // [C] no finite shift: every non-empty read is rescored
+    std::vector<uint64_t> Tc;        // [C]
+    std::vector<double> shift;       // [C] ln(Tb / Tc), 0 where full
+    std::vector<uint64_t> n_resc;    // [C]
+    std::vector<uint2> pairs;        // {read, slot}, read-major
+    std::vector<uint32_t> cand_of, slot_of;
+    std::vector<double> res;         // value per pair
+    const unsigned long long *d_rmask = nullptr;  // on_device: [W][R] read masks
+};
+
+void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, CncJob &job) {
     hipStream_t s = current_stream();
     const uint64_t R = reads->R;
     const uint32_t N = m->N, E = m->E;
     const uint8_t *emis = m->emission.data();
+    const uint32_t *base_cn = job.base_cn, min_cn = job.min_cn, C = job.C;
+    const uint64_t *chg_off = job.chg_off;
+    const uint32_t *chg_node = job.chg_node, *chg_cn = job.chg_cn;
+    const uint64_t Tb = job.Tb;
     auto eff = [&](uint32_t k) { return std::max(k, min_cn); };
-    if (R == 0) {  // (an empty product: ln 1 per candidate, nothing rescored)
-        const std::vector<double> z(C, 0.0);
-        const std::vector<uint64_t> zn(C, 0);
-        put_doubles(out_total, z.data(), C);
-        put_bytes(out_n_rescored, zn.data(), (size_t)C * sizeof(uint64_t));
-        return;
-    }
-
-    // the base: one call of the full form
-    std::vector<double> base(R);
-    double base_tot = 0.0;
-    full_prob_reads_hinted(m, reads, mp, 1, nullptr, nullptr, base.data(), &base_tot, nullptr, base_cn, min_cn);
 
     // effective changes (e differs from the base) and T_c, exact in integers
-    uint64_t Tb = 0;
-    for (uint32_t v = 0; v < N; v++)
-        if (emis[v] != (uint8_t)'n') Tb += eff(base_cn[v]);
     std::vector<uint2> marks;  // {candidate, node}
-    std::vector<uint8_t> full(C, 0);
-    std::vector<double> shift(C, 0.0);
+    std::vector<uint8_t> &full = job.full;
+    std::vector<double> &shift = job.shift;
+    full.assign(C, 0);
+    shift.assign(C, 0.0);
+    job.Tc.assign(C, 0);
     for (uint32_t c = 0; c < C; c++) {
         int64_t dT = 0;
         for (uint64_t j = chg_off[c]; j < chg_off[c + 1]; j++) {
@@ -1201,19 +1224,29 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
             if (emis[v] != (uint8_t)'n') dT += d;
         }
         const uint64_t Tc = (uint64_t)((int64_t)Tb + dT);
+        job.Tc[c] = Tc;
         full[c] = Tb == 0 || Tc == 0;  // (no finite shift: scored in full)
         if (!full[c]) shift[c] = std::log((double)Tb / (double)Tc);
     }
+
+    trace("cnc: effective changes (host)");
 
     // read masks: bit c % 64 of word c / 64 set when the read's lists meet A_c
     const uint32_t W = (C + 63) / 64;
     std::vector<unsigned long long> rmask((size_t)W * R, 0ull);
     DevBuf &d_mask = m->wset().aux[22], &d_list = m->wset().aux[23];
+    DevBuf &d_nrmask = job.on_device ? m->wset().aux[13] : d_mask;  // (d_mask takes the pairs below)
+    if (job.on_device) {
+        d_nrmask.reserve((size_t)W * N * 8 + (size_t)W * R * 8);
+        unsigned long long *rm = d_nrmask.as<unsigned long long>() + (size_t)W * N;
+        if (marks.empty()) HIP_CHECK(hipMemsetAsync(rm, 0, (size_t)W * R * 8, s));
+        job.d_rmask = rm;
+    }
     if (!marks.empty()) {
         const size_t nm_bytes = (size_t)W * N * 8, rm_bytes = (size_t)W * R * 8;
-        d_mask.reserve(nm_bytes + rm_bytes);
+        d_nrmask.reserve(nm_bytes + rm_bytes);
         d_list.reserve(marks.size() * sizeof(uint2));
-        unsigned long long *nm = d_mask.as<unsigned long long>(), *rm = nm + (size_t)W * N;
+        unsigned long long *nm = d_nrmask.as<unsigned long long>(), *rm = nm + (size_t)W * N;
         HIP_CHECK(hipMemsetAsync(nm, 0, nm_bytes, s));
         HIP_CHECK(hipMemcpyAsync(d_list.p, marks.data(), marks.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(cnc_mark, dim3((unsigned)((marks.size() + 255) / 256)), dim3(256), 0, s, d_list.as<uint2>(),
@@ -1225,12 +1258,16 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
         HIP_CHECK(hipStreamSynchronize(s));
     }
 
+    trace("cnc: mark + read masks");
+
     // work list: (read, candidate) pairs, read-major, candidates ascending; slot = rank among the candidates with a pair
     std::vector<unsigned long long> fullw(W, 0ull);
     for (uint32_t c = 0; c < C; c++)
         if (full[c]) fullw[c >> 6] |= 1ull << (c & 63);
-    std::vector<uint64_t> n_resc(C, 0);
-    std::vector<uint2> pairs;  // {read, candidate}, then {read, slot}
+    std::vector<uint64_t> &n_resc = job.n_resc;
+    n_resc.assign(C, 0);
+    std::vector<uint2> &pairs = job.pairs;  // {read, candidate}, then {read, slot}
+    pairs.clear();
     std::vector<uint64_t> read_pair_off(R + 1, 0);
     for (uint64_t r = 0; r < R; r++) {
         read_pair_off[r] = pairs.size();
@@ -1246,7 +1283,9 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
         }
     }
     read_pair_off[R] = pairs.size();
-    std::vector<uint32_t> slot_of(C, 0xffffffffu), cand_of;
+    std::vector<uint32_t> &slot_of = job.slot_of, &cand_of = job.cand_of;
+    slot_of.assign(C, 0xffffffffu);
+    cand_of.clear();
     for (uint32_t c = 0; c < C; c++)
         if (n_resc[c]) {
             slot_of[c] = (uint32_t)cand_of.size();
@@ -1255,7 +1294,9 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
     const uint32_t D = (uint32_t)cand_of.size();
     for (auto &q : pairs) q.y = slot_of[q.y];
 
-    std::vector<double> res(pairs.size());
+    std::vector<double> &res = job.res;
+    res.assign(pairs.size(), 0.0);
+    trace("cnc: pair list (host)");
     EvTimer tm(timing_enabled());
     if (D) {
         // init / trans of the D dirty candidates: the base vector plus their changes, then the full form's cn_totals /
@@ -1272,16 +1313,17 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
         cand_trans.reserve(std::max<size_t>(ne, 1) * sizeof(double));
         const size_t apply_at = ((size_t)N * sizeof(uint32_t) + 255) / 256 * 256;
         d_list.reserve(apply_at + std::max<size_t>(apply.size(), 1) * sizeof(uint3));
-        uint32_t *d_base = d_list.as<uint32_t>();
+        const uint32_t *d_base = job.d_base ? job.d_base : d_list.as<uint32_t>();
         uint3 *d_apply = (uint3 *)(d_list.as<char>() + apply_at);
         uint32_t *d_cn = staging.as<uint32_t>();
         unsigned long long *d_tot = (unsigned long long *)(staging.as<char>() + tot_at);
-        HIP_CHECK(hipMemcpyAsync(d_base, base_cn, N * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (!job.d_base)
+            HIP_CHECK(hipMemcpyAsync(d_list.p, base_cn, N * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         if (!apply.empty())
             HIP_CHECK(hipMemcpyAsync(d_apply, apply.data(), apply.size() * sizeof(uint3), hipMemcpyHostToDevice, s));
         HIP_CHECK(hipMemsetAsync(d_tot, 0, D * sizeof(unsigned long long), s));
         const unsigned nb = (unsigned)((N + 255) / 256);
-        hipLaunchKernelGGL(cnc_expand, dim3(nb, D), dim3(256), 0, s, (const uint32_t *)d_base, N, d_cn);
+        hipLaunchKernelGGL(cnc_expand, dim3(nb, D), dim3(256), 0, s, d_base, N, d_cn);
         if (!apply.empty())
             hipLaunchKernelGGL(cnc_apply, dim3((unsigned)((apply.size() + 255) / 256)), dim3(256), 0, s,
                                (const uint3 *)d_apply, (uint32_t)apply.size(), N, d_cn);
@@ -1291,6 +1333,7 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
                            m->dev.chi_off.as<uint32_t>(), m->dev.chi_node.as<uint32_t>(), m->dev.chi_edge.as<uint32_t>(), N, E,
                            min_cn, (const unsigned long long *)d_tot, cand_init.as<double>(), cand_trans.as<double>());
         HIP_CHECK(hipGetLastError());
+        trace("cnc: expand + cn_probs");
 
         // the pairs, and the [D][R] result planes of the kernels
         DevBuf &d_ids = m->wset().aux[10], &d_out = m->wset().aux[11], &d_err = m->wset().aux[12];
@@ -1386,6 +1429,7 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
                     cls[0].push_back(rd);
                 }
         }
+        trace("cnc: packed classes");
         // one-candidate classes; a read any of whose pairs overflows a class is promoted.  The lean class takes one
         // {read, slot} pair per wave.  The generic kernels (lists over 64 nodes, or degree above ADJ_DEG; few reads) run
         // as in the full form, over the class's reads x the D candidates, and only the pairs are read back: a pair-list
@@ -1426,6 +1470,7 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
             }
         }
         gather(true);
+        trace("cnc: one-candidate classes");
         // pairs that came back -inf: the wide-range pass of full_prob_reads_hinted (short lists first)
         if (!knobs().no_exact_hinted) {
             std::vector<size_t> xq;
@@ -1448,6 +1493,9 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
                 if (n_small < xs.size())
                     hipLaunchKernelGGL((hinted_exact_kernel<PHMM_MAX_ACTIVE_NODES, 1024>), dim3((unsigned)(xs.size() - n_small)),
                                        dim3(64), 0, s, a, (const uint2 *)(dp + n_small), dres + n_small);
+                if (job.on_device)
+                    hipLaunchKernelGGL(cnc_scatter, dim3((unsigned)((xs.size() + 255) / 256)), dim3(256), 0, s,
+                                       (const uint2 *)dp, (const double *)dres, xs.size(), R, d_out.as<double>());
                 HIP_CHECK(hipGetLastError());
                 std::vector<double> hres(xs.size());
                 HIP_CHECK(hipMemcpyAsync(hres.data(), dres, hres.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1459,6 +1507,47 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
         }
     }
     stats().ms[2] += tm.stop();  // (on top of the base pass; cells stay those of the base pass)
+    trace("cnc: exact pass");
+}
+
+}  // namespace
+
+void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp,
+                                      const uint32_t *base_cn, uint32_t min_cn, uint32_t C, const uint64_t *chg_off,
+                                      const uint32_t *chg_node, const uint32_t *chg_cn, double *out_logp,
+                                      double *out_total, uint64_t *out_n_rescored) {
+    const uint64_t R = reads->R;
+    const uint32_t N = m->N;
+    const uint8_t *emis = m->emission.data();
+    if (R == 0) {  // (an empty product: ln 1 per candidate, nothing rescored)
+        const std::vector<double> z(C, 0.0);
+        const std::vector<uint64_t> zn(C, 0);
+        put_doubles(out_total, z.data(), C);
+        put_bytes(out_n_rescored, zn.data(), (size_t)C * sizeof(uint64_t));
+        return;
+    }
+
+    // the base: one call of the full form
+    trace("cnc: enter");
+    std::vector<double> base(R);
+    double base_tot = 0.0;
+    full_prob_reads_hinted(m, reads, mp, 1, nullptr, nullptr, base.data(), &base_tot, nullptr, base_cn, min_cn);
+
+    trace("cnc: base pass");
+    CncJob job;
+    job.base_cn = base_cn;
+    for (uint32_t v = 0; v < N; v++)
+        if (emis[v] != (uint8_t)'n') job.Tb += std::max(base_cn[v], min_cn);
+    job.min_cn = min_cn;
+    job.C = C;
+    job.chg_off = chg_off;
+    job.chg_node = chg_node;
+    job.chg_cn = chg_cn;
+    trace("cnc: T_base (host sum)");
+    cnc_score(m, reads, mp, job);
+    const std::vector<uint8_t> &full = job.full;
+    const std::vector<double> &shift = job.shift, &res = job.res;
+    const std::vector<uint2> &pairs = job.pairs;
 
     // clean reads: base + ln(T_base / T_c); the rescored pairs over them; totals in read order, as the full form sums
     std::vector<double> out((size_t)C * R);
@@ -1467,12 +1556,233 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
         double *o = out.data() + (size_t)c * R;
         for (uint64_t r = 0; r < R; r++) o[r] = (full[c] || reads->off[r + 1] == reads->off[r]) ? base[r] : base[r] + shift[c];
     }
-    for (size_t q = 0; q < pairs.size(); q++) out[(size_t)cand_of[pairs[q].y] * R + pairs[q].x] = res[q];
+    for (size_t q = 0; q < pairs.size(); q++) out[(size_t)job.cand_of[pairs[q].y] * R + pairs[q].x] = res[q];
     for (uint32_t c = 0; c < C; c++)
         for (uint64_t r = 0; r < R; r++) tot[c] += out[(size_t)c * R + r];
     put_doubles(out_logp, out.data(), out.size());
     put_doubles(out_total, tot.data(), C);
-    put_bytes(out_n_rescored, n_resc.data(), (size_t)C * sizeof(uint64_t));
+    put_bytes(out_n_rescored, job.n_resc.data(), (size_t)C * sizeof(uint64_t));
+    trace("cnc: compose [C][R] (host)");
+}
+
+// ---------------------------------------------------------------- phmm_likelihood: the sampler's state on the device
+// The greedy search of sample_posterior (posterior.rs:314-417) at one k: score the neighbours of the current vector
+// (sample_posterior_once, posterior.rs:470-528), move to one or to the union of several (posterior.rs:532-590), repeat.
+// The handle keeps the vector and, per read, val[r] / T_at[r] (phmm_internal.h); a candidate batch is cnc_score against
+// them with no base pass, and a move is cnc_score of one candidate whose results are written back.  DESIGN.md section 6.
+
+struct LkCand {
+    unsigned long long Tc;
+    uint32_t slot;  // plane of the candidate's rescored reads in the [D][R] results
+    uint32_t full;
+};
+// block c: out[c][r] = the plane's value where (c, r) was rescored, else val[r] + ln(T_at[r] / T_c); tot[c] = their sum,
+// thread-strided partial sums reduced over a fixed tree (the same bits on every call).  rmask == nullptr: nothing rescored.
+__global__ void __launch_bounds__(256) lk_compose(const LkCand *cand, const uint64_t *read_off, uint64_t R,
+                                                  const double *val, const unsigned long long *tat,
+                                                  const unsigned long long *rmask, const double *plane, double *out,
+                                                  double *tot) {
+    const uint32_t c = blockIdx.x;
+    const LkCand k = cand[c];
+    const unsigned long long *w = rmask ? rmask + (size_t)(c >> 6) * R : nullptr;
+    double s = 0.0;
+    for (uint64_t r = threadIdx.x; r < R; r += 256) {
+        double v = val[r];
+        if (read_off[r + 1] != read_off[r]) {
+            if (k.full || (w && ((w[r] >> (c & 63)) & 1ull))) v = plane[(size_t)k.slot * R + r];
+            else if (tat[r] != k.Tc) v += log((double)tat[r] / (double)k.Tc);
+        }
+        if (out) out[(size_t)c * R + r] = v;
+        s += v;
+    }
+    __shared__ double sh[256];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tot[c] = sh[0];
+}
+// a move: the reads it rescored take the plane's value and the T of the new vector
+__global__ void __launch_bounds__(256) lk_commit(const uint64_t *read_off, uint64_t R, const unsigned long long *rmask,
+                                                 uint32_t full, const double *plane, unsigned long long T_new,
+                                                 double *val, unsigned long long *tat) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= R || read_off[r + 1] == read_off[r]) return;
+    if (full || (rmask[r] & 1ull)) {
+        val[r] = plane[r];
+        tat[r] = T_new;
+    }
+}
+
+namespace {
+
+// values and total of the handle's state (or of a scored batch) through lk_compose, into aux[14]: cand | tot | out
+struct Composed {
+    const double *tot, *out;
+};
+Composed lk_run_compose(const phmm_likelihood *lk, const std::vector<LkCand> &cand, const unsigned long long *rmask,
+                        bool want_out) {
+    hipStream_t s = current_stream();
+    const uint64_t R = lk->reads->R;
+    const size_t C = cand.size();
+    DevBuf &buf = lk->m->wset().aux[14];
+    const size_t tot_at = (C * sizeof(LkCand) + 255) / 256 * 256, out_at = tot_at + (C * sizeof(double) + 255) / 256 * 256;
+    buf.reserve(out_at + (want_out ? C * R * sizeof(double) : 0));
+    LkCand *d_cand = buf.as<LkCand>();
+    double *d_tot = (double *)(buf.as<char>() + tot_at);
+    double *d_o = want_out ? (double *)(buf.as<char>() + out_at) : nullptr;
+    HIP_CHECK(hipMemcpyAsync(d_cand, cand.data(), C * sizeof(LkCand), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(lk_compose, dim3((unsigned)C), dim3(256), 0, s, (const LkCand *)d_cand,
+                       lk->reads->d_off.as<uint64_t>(), R, (const double *)lk->d_val.as<double>(),
+                       (const unsigned long long *)lk->d_tat.as<unsigned long long>(), rmask,
+                       (const double *)lk->m->wset().aux[11].as<double>(), d_o, d_tot);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));  // (cand is the caller's)
+    return Composed{d_tot, d_o};
+}
+
+void lk_prepare(const phmm_likelihood *lk) {
+    upload_reads(lk->reads);
+    upload_mappings(lk->mp);
+    ensure_logib(lk->m, lk->reads->max_len + 1);
+    stats() = CallStats();
+}
+
+}  // namespace
+
+void likelihood_refresh(phmm_likelihood *lk) {
+    const uint64_t R = lk->reads->R;
+    uint64_t T = 0;
+    for (uint32_t v = 0; v < lk->m->N; v++)
+        if (lk->m->emission[v] != (uint8_t)'n') T += std::max(lk->cn[v], lk->min_cn);
+    if (R) {
+        std::vector<double> val(R);
+        double tot = 0.0;
+        full_prob_reads_hinted(lk->m, lk->reads, lk->mp, 1, nullptr, nullptr, val.data(), &tot, nullptr, lk->cn.data(),
+                               lk->min_cn);
+        const std::vector<unsigned long long> tat(R, T);
+        hipStream_t s = current_stream();
+        HIP_CHECK(hipMemcpyAsync(lk->d_val.p, val.data(), R * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(lk->d_tat.p, tat.data(), R * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+    lk->T = T;
+}
+
+void likelihood_score_changes(phmm_likelihood *lk, uint32_t C, const uint64_t *chg_off, const uint32_t *chg_node,
+                              const uint32_t *chg_cn, double *out_logp, double *out_total, uint64_t *out_n_rescored) {
+    const uint64_t R = lk->reads->R;
+    if (R == 0) {
+        const std::vector<double> z(C, 0.0);
+        const std::vector<uint64_t> zn(C, 0);
+        put_doubles(out_total, z.data(), C);
+        put_bytes(out_n_rescored, zn.data(), (size_t)C * sizeof(uint64_t));
+        return;
+    }
+    lk_prepare(lk);
+    trace("lk: enter");
+    CncJob job;
+    job.base_cn = lk->cn.data();
+    job.d_base = lk->d_cn.as<uint32_t>();
+    job.Tb = lk->T;
+    job.min_cn = lk->min_cn;
+    job.C = C;
+    job.chg_off = chg_off;
+    job.chg_node = chg_node;
+    job.chg_cn = chg_cn;
+    job.on_device = true;
+    cnc_score(lk->m, lk->reads, lk->mp, job);
+
+    std::vector<LkCand> cand(C);
+    for (uint32_t c = 0; c < C; c++) cand[c] = LkCand{job.Tc[c], job.slot_of[c], job.full[c]};
+    const Composed r = lk_run_compose(lk, cand, job.d_rmask, out_logp != nullptr);
+    copy_out(out_logp, r.out, (size_t)C * R * sizeof(double));
+    copy_out(out_total, r.tot, (size_t)C * sizeof(double));
+    put_bytes(out_n_rescored, job.n_resc.data(), (size_t)C * sizeof(uint64_t));
+    trace("lk: compose (device)");
+}
+
+void likelihood_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_node, const uint32_t *chg_cn,
+                     double *out_total, uint64_t *out_n_rescored) {
+    hipStream_t s = current_stream();
+    const uint64_t R = lk->reads->R;
+    const uint32_t N = lk->m->N;
+    uint64_t n_resc = 0;
+    if (n_chg) {
+        const uint64_t off[2] = {0, n_chg};
+        CncJob job;
+        job.base_cn = lk->cn.data();
+        job.d_base = lk->d_cn.as<uint32_t>();
+        job.Tb = lk->T;
+        job.min_cn = lk->min_cn;
+        job.C = 1;
+        job.chg_off = off;
+        job.chg_node = chg_node;
+        job.chg_cn = chg_cn;
+        job.on_device = true;
+        uint64_t T_new = 0;
+        if (R) {
+            lk_prepare(lk);
+            cnc_score(lk->m, lk->reads, lk->mp, job);
+            T_new = job.Tc[0];
+            n_resc = job.n_resc[0];
+        } else {
+            int64_t dT = 0;
+            for (uint64_t j = 0; j < n_chg; j++)
+                if (lk->m->emission[chg_node[j]] != (uint8_t)'n')
+                    dT += (int64_t)std::max(chg_cn[j], lk->min_cn) - (int64_t)std::max(lk->cn[chg_node[j]], lk->min_cn);
+            T_new = (uint64_t)((int64_t)lk->T + dT);
+        }
+        // the total under the new vector, before anything changes: the move's own planes and mask over the old state
+        // (the bits phmm_likelihood_current returns afterwards: the same values reduced over the same tree)
+        std::vector<uint3> apply(n_chg);
+        for (uint64_t j = 0; j < n_chg; j++) apply[j] = make_uint3(0, chg_node[j], chg_cn[j]);
+        DevBuf &d_apply = lk->m->wset().aux[14];
+        d_apply.reserve(std::max<size_t>(apply.size() * sizeof(uint3), 512));  // (lk_run_compose's own need: no growth below)
+        double total = 0.0;
+        if (R) {
+            const std::vector<LkCand> cand(1, LkCand{T_new, job.slot_of[0], job.full[0]});
+            const Composed r = lk_run_compose(lk, cand, job.d_rmask, false);
+            HIP_CHECK(hipMemcpyAsync(&total, r.tot, sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
+        HIP_CHECK(hipMemcpyAsync(d_apply.p, apply.data(), apply.size() * sizeof(uint3), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        // everything that can fail is behind us: the state changes here, in stream order
+        if (n_resc)
+            hipLaunchKernelGGL(lk_commit, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s,
+                               lk->reads->d_off.as<uint64_t>(), R, job.d_rmask, (uint32_t)job.full[0],
+                               (const double *)lk->m->wset().aux[11].as<double>(), (unsigned long long)T_new,
+                               lk->d_val.as<double>(), lk->d_tat.as<unsigned long long>());
+        hipLaunchKernelGGL(cnc_apply, dim3((unsigned)((apply.size() + 255) / 256)), dim3(256), 0, s,
+                           (const uint3 *)d_apply.as<uint3>(), (uint32_t)apply.size(), N, lk->d_cn.as<uint32_t>());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));
+        for (uint64_t j = 0; j < n_chg; j++) lk->cn[chg_node[j]] = chg_cn[j];
+        lk->T = T_new;
+        put_doubles(out_total, &total, 1);
+    } else if (out_total) {
+        likelihood_current(lk, nullptr, nullptr, out_total);
+    }
+    put_bytes(out_n_rescored, &n_resc, sizeof(uint64_t));
+}
+
+void likelihood_current(const phmm_likelihood *lk, uint32_t *out_cn, double *out_logp, double *out_total) {
+    const uint64_t R = lk->reads->R;
+    if (out_cn && lk->m->N) std::memcpy(out_cn, lk->cn.data(), (size_t)lk->m->N * sizeof(uint32_t));
+    if (!out_logp && !out_total) return;
+    if (R == 0) {
+        const double zero = 0.0;
+        put_doubles(out_total, &zero, 1);
+        return;
+    }
+    upload_reads(lk->reads);
+    const std::vector<LkCand> cand(1, LkCand{lk->T, 0, 0});
+    const Composed r = lk_run_compose(lk, cand, nullptr, out_logp != nullptr);
+    copy_out(out_logp, r.out, R * sizeof(double));
+    copy_out(out_total, r.tot, sizeof(double));
 }
 
 

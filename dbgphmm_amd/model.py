@@ -328,6 +328,12 @@ class PHMMModel:
             _ptr(node), _ptr(cn), _ptr(lp), _ptr(tot), _ptr(nr)))
         return tot, lp, nr
 
+    def likelihood(self, reads: ReadCollection, mappings: Mappings, copy_nums: np.ndarray,
+                   min_copy_num: int = 0) -> "Likelihood":
+        """MultiDbg::to_likelihood (posterior.rs:247-255) as a device-resident state for the greedy search of
+        sample_posterior (posterior.rs:314-417): see Likelihood."""
+        return Likelihood(self, reads, mappings, copy_nums, min_copy_num)
+
     def generate_mappings(self, reads: ReadCollection, mappings: Optional[Mappings] = None,
                           use_max_ratio: bool = True, out_node_freq=None):
         """PHMMModel::generate_mappings (hint.rs:193-220) -> (Mappings, node_freq[N])."""
@@ -347,6 +353,70 @@ def copy_num_changes(base: np.ndarray, candidates: np.ndarray):
     off = np.zeros(cands.shape[0] + 1, dtype=np.uint64)
     np.cumsum(np.bincount(ci, minlength=cands.shape[0]), out=off[1:])
     return off, node.astype(np.uint32), cands[ci, node].astype(np.uint32)
+
+
+class Likelihood:
+    """The sampler's state at one k, on the device: the current copy-number vector and every read's ln P under it,
+    for the whole greedy search of sample_posterior (multi_dbg/posterior.rs:314-417).  score_changes is the loop of
+    sample_posterior_once over the neighbours of the current vector (posterior.rs:470-528) without a base pass; move
+    is the step to the best neighbour or to the union of several independent moves (posterior.rs:532-600), rescoring
+    only the reads the move touches.  Borrows model, reads and mappings (kept alive here)."""
+
+    def __init__(self, model: "PHMMModel", reads: ReadCollection, mappings: Mappings, copy_nums: np.ndarray,
+                 min_copy_num: int = 0):
+        self.model, self.reads, self.mappings = model, reads, mappings
+        cn = np.ascontiguousarray(copy_nums, dtype=np.uint32).reshape(-1)
+        if cn.size != model.n_nodes:
+            raise ValueError("copy_nums must have one entry per node")
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().phmm_likelihood_create(model._h, reads._h, mappings._h if mappings else None, _ptr(cn),
+                                                     int(min_copy_num), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _ffi.lib().phmm_likelihood_destroy(self._h)
+            self._h = None
+
+    def score_changes(self, changes, out_logp=None, per_read: bool = True):
+        """Candidates as changes to the CURRENT vector, changes = (off[C+1], node, cn) as copy_num_changes builds them
+        (sample_posterior_once, posterior.rs:470-528) -> (totals[C], per_read[C,R] or None, n_rescored[C]).
+        per_read=False forms no [C,R] matrix anywhere."""
+        off, node, cn = changes
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        node = np.ascontiguousarray(node, dtype=np.uint32)
+        cn = np.ascontiguousarray(cn, dtype=np.uint32)
+        Cn = off.size - 1
+        lp = out_logp if out_logp is not None else (np.empty((Cn, len(self.reads))) if per_read else None)
+        tot = np.empty(Cn)
+        nr = np.empty(Cn, dtype=np.uint64)
+        _ffi.check(_ffi.lib().phmm_likelihood_score_changes(self._h, Cn, _ptr(off), _ptr(node), _ptr(cn), _ptr(lp),
+                                                            _ptr(tot), _ptr(nr)))
+        return tot, lp, nr
+
+    def move(self, nodes, copy_nums):
+        """current[nodes] = copy_nums: one candidate of the last batch or the union of several (posterior.rs:532-600)
+        -> (ln P(R | new vector), reads rescored)."""
+        node = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1)
+        cn = np.ascontiguousarray(copy_nums, dtype=np.uint32).reshape(-1)
+        if node.size != cn.size:
+            raise ValueError("nodes and copy_nums differ in length")
+        tot = np.empty(1)
+        nr = np.empty(1, dtype=np.uint64)
+        _ffi.check(_ffi.lib().phmm_likelihood_move(self._h, node.size, _ptr(node), _ptr(cn), _ptr(tot), _ptr(nr)))
+        return float(tot[0]), int(nr[0])
+
+    def current(self):
+        """-> (copy_nums[N], per-read ln P [R], their sum) under the current vector."""
+        cn = np.empty(self.model.n_nodes, dtype=np.uint32)
+        lp = np.empty(len(self.reads))
+        tot = np.zeros(1)
+        _ffi.check(_ffi.lib().phmm_likelihood_current(self._h, _ptr(cn), _ptr(lp), _ptr(tot)))
+        return cn, lp, float(tot[0])
+
+    def refresh(self) -> None:
+        """Rescore the current vector in full (after PHMMModel.set_params)."""
+        _ffi.check(_ffi.lib().phmm_likelihood_refresh(self._h))
 
 
 class PHMMOutput:

@@ -234,6 +234,49 @@ int phmm_full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads
         uint32_t n_candidates, const uint64_t *change_off, const uint32_t *change_node,
         const uint32_t *change_copy_num, double *out_logp, double *out_total, uint64_t *out_n_rescored);
 
+/* ---- the sampler's state on the device -------------------------------------------
+ * MultiDbg::to_likelihood (multi_dbg/posterior.rs:247-255) through the greedy search of sample_posterior
+ * (posterior.rs:314-417): score every neighbour of the current copy-number vector (sample_posterior_once,
+ * posterior.rs:470-528), move to the best one or to the union of several independent moves (posterior.rs:532-590),
+ * repeat from there.  The handle keeps the current vector and every read's ln P under it on the device for the whole
+ * search at one k: candidates are scored against them with no base pass and no upload of the vector, and a move
+ * rescores only the reads it touches.
+ * The handle BORROWS model, reads and mappings: they must outlive it.  Its own arrays belong to the handle, not to
+ * the device workspace (phmm_release_workspace between two calls changes no result).  Every call takes the device
+ * lock.  A call that fails (PHMM_EINVAL for what phmm_full_prob_reads_copy_num_changes refuses, or any other error)
+ * writes no output and leaves the vector, T and the per-read values as they were.  phmm_model_set_probs does not
+ * concern the handle (init / trans come from copy numbers); after phmm_model_set_params call phmm_likelihood_refresh. */
+typedef struct phmm_likelihood phmm_likelihood;
+
+/* Scores copy_nums[N] (host) in full once -- phmm_full_prob_reads_copy_nums with one candidate -- and keeps the
+ * vector, T = sum of max(cn, min_copy_num) over the emittable nodes, and every read's ln P under it. */
+int phmm_likelihood_create(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mappings,
+                           const uint32_t *copy_nums, uint32_t min_copy_num, phmm_likelihood **out);
+
+/* C candidates as changes to the CURRENT vector (the CSR of phmm_full_prob_reads_copy_num_changes, host pointers).
+ * Returns what that call returns with the current vector as its base: the same reads rescored per candidate, rescored
+ * (read, candidate) pairs bit-equal to phmm_full_prob_reads_copy_nums on the materialised vector, every other pair
+ * ln P_current + ln(T / T_c).  out_logp [C][R] / out_total [C] / out_n_rescored [C]: NULL, host or device; with
+ * out_logp == NULL no [C][R] matrix is formed.  n_candidates = 0 writes nothing. */
+int phmm_likelihood_score_changes(phmm_likelihood *lk, uint32_t n_candidates, const uint64_t *change_off,
+                                  const uint32_t *change_node, const uint32_t *change_copy_num,
+                                  double *out_logp, double *out_total, uint64_t *out_n_rescored);
+
+/* The current vector becomes current + changes (any change list: one candidate of the last batch, or the union of
+ * several, posterior.rs:565-590).  Rescores the reads the move touches (bit-equal to phmm_full_prob_reads_copy_nums on
+ * the new vector), shifts the others by ln(T_old / T_new) without accumulating rounding over a chain of moves, updates T.
+ * out_total = sum of ln P under the new vector; out_n_rescored = reads run through the kernels; NULL, host or
+ * device.  n_changes = 0 changes nothing. */
+int phmm_likelihood_move(phmm_likelihood *lk, uint64_t n_changes, const uint32_t *change_node,
+                         const uint32_t *change_copy_num, double *out_total, uint64_t *out_n_rescored);
+
+/* What the handle holds: copy_nums[N] (host), per-read ln P [R], their sum (host or device).  Any may be NULL. */
+int phmm_likelihood_current(const phmm_likelihood *lk, uint32_t *out_copy_nums, double *out_logp, double *out_total);
+
+/* Rescores the current vector in full (after phmm_model_set_params, or to drop the one rounding of shifted reads). */
+int phmm_likelihood_refresh(phmm_likelihood *lk);
+void phmm_likelihood_destroy(phmm_likelihood *lk);
+
 /* PHMMModel::to_full_prob_sparse_backward (freq.rs:153-163): ln P(read) from PHMMModel::backward_sparse
  * (backward.rs:146-185) -- dense b_step over the last n_warmup positions, then the backward recursion on
  * its own frontier: top_nodes(n_active_nodes) of the previous column, adaptive b_step (backward.rs:216-261).

@@ -307,10 +307,16 @@ impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
 /// copy numbers (PHMM node id = full-edge id, multi_dbg.rs:1569-1576) and init / trans are derived on the device as
 /// SeqGraph::to_phmm does (seq_graph.rs:110-135, 160-209).
 pub struct AmdLikelihood {
+    state: *mut phmm_likelihood,  // (first: dropped before the model, reads and mappings it borrows)
     model: AmdModel,
     reads: AmdReads,
     mappings: AmdMappings,
     n_nodes: usize,
+}
+impl Drop for AmdLikelihood {
+    fn drop(&mut self) {
+        unsafe { phmm_likelihood_destroy(self.state) }
+    }
 }
 impl AmdLikelihood {
     pub fn new<N: PHMMNode, E: PHMMEdge, S: Seq>(phmm: &PHMMModel<N, E>, reads: &ReadCollection<S>,
@@ -318,7 +324,7 @@ impl AmdLikelihood {
         let model = AmdModel::new(phmm);
         let r = AmdReads::new(reads);
         let mp = AmdMappings::from_mappings(&r, mappings);
-        AmdLikelihood { model, reads: r, mappings: mp, n_nodes: phmm.n_nodes() }
+        AmdLikelihood { state: ptr::null_mut(), model, reads: r, mappings: mp, n_nodes: phmm.n_nodes() }
     }
     /// copy_nums: candidates x n_nodes, row-major -> ln P(R | X_c) per candidate (Score.likelihood, posterior.rs:259-277)
     pub fn likelihoods(&mut self, copy_nums: &[u32], min_copy_num: u32) -> Vec<Prob> {
@@ -346,5 +352,44 @@ impl AmdLikelihood {
                                                   ptr::null_mut(), totals.as_mut_ptr(), rescored.as_mut_ptr())
         });
         (totals.into_iter().map(Prob::from_log_prob).collect(), rescored)
+    }
+
+    // ---- the greedy search of sample_posterior (posterior.rs:314-417) with the sampler's state on the device
+    /// Start of the search at this k: scores `copy_nums` in full once and keeps the vector and every read's ln P
+    /// under it on the device (phmm_likelihood_create) -> ln P(R | X).  A second call starts over from a new vector.
+    pub fn begin(&mut self, copy_nums: &[u32], min_copy_num: u32) -> Prob {
+        assert!(copy_nums.len() == self.n_nodes);
+        unsafe { phmm_likelihood_destroy(self.state) };
+        self.state = ptr::null_mut();
+        check(unsafe {
+            phmm_likelihood_create(self.model.0, self.reads.h, self.mappings.0, copy_nums.as_ptr(), min_copy_num,
+                                   &mut self.state)
+        });
+        let mut total = 0f64;
+        check(unsafe { phmm_likelihood_current(self.state, ptr::null_mut(), ptr::null_mut(), &mut total) });
+        Prob::from_log_prob(total)
+    }
+    /// sample_posterior_once (posterior.rs:470-528): the neighbours of the CURRENT vector, neighbour c sets node[j] to
+    /// cn[j] for j in off[c]..off[c+1].  No base pass, no upload of the vector -> (ln P(R | X_c), reads rescored).
+    pub fn likelihoods_of_neighbors(&mut self, off: &[u64], node: &[u32], cn: &[u32]) -> (Vec<Prob>, Vec<u64>) {
+        assert!(!self.state.is_null() && !off.is_empty() && node.len() == cn.len());
+        let c = off.len() - 1;
+        let mut totals = vec![0f64; c];
+        let mut rescored = vec![0u64; c];
+        check(unsafe {
+            phmm_likelihood_score_changes(self.state, c as u32, off.as_ptr(), node.as_ptr(), cn.as_ptr(),
+                                          ptr::null_mut(), totals.as_mut_ptr(), rescored.as_mut_ptr())
+        });
+        (totals.into_iter().map(Prob::from_log_prob).collect(), rescored)
+    }
+    /// The move (posterior.rs:532-590): the current vector becomes current + changes -- one neighbour of the last
+    /// batch, or the union of several independent improving moves -> ln P(R | new vector).
+    pub fn accept(&mut self, node: &[u32], cn: &[u32]) -> Prob {
+        assert!(!self.state.is_null() && node.len() == cn.len());
+        let mut total = 0f64;
+        check(unsafe {
+            phmm_likelihood_move(self.state, node.len() as u64, node.as_ptr(), cn.as_ptr(), &mut total, ptr::null_mut())
+        });
+        Prob::from_log_prob(total)
     }
 }

@@ -56,6 +56,10 @@ pub struct phmm_reads {
 pub struct phmm_mappings {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct phmm_likelihood {
+    _p: [u8; 0],
+}
 
 #[link(name = "phmm_amd")]
 extern "C" {
@@ -119,6 +123,17 @@ extern "C" {
                                                  change_node: *const u32, change_copy_num: *const u32,
                                                  out_logp: *mut f64, out_total: *mut f64,
                                                  out_n_rescored: *mut u64) -> c_int;
+    pub fn phmm_likelihood_create(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                  copy_nums: *const u32, min_copy_num: u32, out: *mut *mut phmm_likelihood) -> c_int;
+    pub fn phmm_likelihood_score_changes(lk: *mut phmm_likelihood, n_candidates: u32, change_off: *const u64,
+                                         change_node: *const u32, change_copy_num: *const u32, out_logp: *mut f64,
+                                         out_total: *mut f64, out_n_rescored: *mut u64) -> c_int;
+    pub fn phmm_likelihood_move(lk: *mut phmm_likelihood, n_changes: u64, change_node: *const u32,
+                                change_copy_num: *const u32, out_total: *mut f64, out_n_rescored: *mut u64) -> c_int;
+    pub fn phmm_likelihood_current(lk: *const phmm_likelihood, out_copy_nums: *mut u32, out_logp: *mut f64,
+                                   out_total: *mut f64) -> c_int;
+    pub fn phmm_likelihood_refresh(lk: *mut phmm_likelihood) -> c_int;
+    pub fn phmm_likelihood_destroy(lk: *mut phmm_likelihood);
     pub fn phmm_full_prob_sparse_backward(m: *mut phmm_model, reads: *const phmm_reads, out_logp: *mut f64,
                                           out_total: *mut f64) -> c_int;
     pub fn phmm_run_sparse(m: *mut phmm_model, reads: *const phmm_reads, out_logp_forward: *mut f64,
