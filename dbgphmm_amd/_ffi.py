@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("PHMM_AMD_LIB") or os.path.join(_HERE, "libphmm_amd.so
 CSRC = os.path.join(_HERE, "csrc")
 
 PHMM_OK, PHMM_EINVAL, PHMM_ENODEVICE, PHMM_ENOMEM, PHMM_ECAPACITY, PHMM_EINTERNAL = 0, -1, -2, -3, -4, -5
+PHMM_GROUP_MIXED = 0xFFFFFFFF  # phmm_likelihood_current_groups: a node-form move changed part of the group
 PHMM_READ_DEFERRED, PHMM_READ_WIDE_FRONTIER, PHMM_READ_FORCED_SWITCH = 1, 2, 4  # phmm_reads_last_call_info flags
 
 
@@ -90,6 +91,10 @@ def lib():
         "phmm_likelihood_current": (i32, [vp, vp, vp, vp]),
         "phmm_likelihood_refresh": (i32, [vp]),
         "phmm_likelihood_destroy": (None, [vp]),
+        "phmm_likelihood_set_groups": (i32, [vp, u32, vp, vp]),
+        "phmm_likelihood_score_group_changes": (i32, [vp, u32, vp, vp, vp, vp, vp, vp]),
+        "phmm_likelihood_move_groups": (i32, [vp, u64, vp, vp, vp, vp]),
+        "phmm_likelihood_current_groups": (i32, [vp, vp]),
         "phmm_generate_mappings": (i32, [vp, vp, vp, i32, P(vp), vp]),
         "phmm_run_with_mapping_edges": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_last_call_stats": (i32, [i32, P(dbl), P(u64), P(u64)]),
@@ -116,6 +121,8 @@ DECLARED_SYMBOLS = [
     "phmm_enable_timing",
     "phmm_likelihood_create", "phmm_likelihood_score_changes", "phmm_likelihood_move", "phmm_likelihood_current",
     "phmm_likelihood_refresh", "phmm_likelihood_destroy",
+    "phmm_likelihood_set_groups", "phmm_likelihood_score_group_changes", "phmm_likelihood_move_groups",
+    "phmm_likelihood_current_groups",
 ]
 
 

@@ -827,6 +827,134 @@ int phmm_likelihood_refresh(phmm_likelihood *lk) {
     return guarded_on(lk->m, [&] { likelihood_refresh(lk); });
 }
 
+// ---- node groups on the handle: the checks and the tables here, the group flavours of the kernels in sparse.hip
+int phmm_likelihood_set_groups(phmm_likelihood *lk, uint32_t n_groups, const uint64_t *group_off,
+                               const uint32_t *group_nodes) {
+    if (!lk) return fail(PHMM_EINVAL, "NULL likelihood handle");
+    return guarded_on(lk->m, [&] {
+        const uint32_t N = lk->m->N, G = n_groups, NONE = PHMM_GROUP_MIXED;
+        if (G == NONE) PHMM_THROW(PHMM_EINVAL, "too many groups");
+        if (G && !group_off) PHMM_THROW(PHMM_EINVAL, "NULL group_off");
+        if (G && group_off[0] != 0) PHMM_THROW(PHMM_EINVAL, "group_off[0] must be 0");
+        for (uint32_t g = 0; g < G; g++)
+            if (group_off[g + 1] < group_off[g]) PHMM_THROW(PHMM_EINVAL, "group_off decreases");
+        const uint64_t n_in = G ? group_off[G] : 0;
+        if (n_in > N) PHMM_THROW(PHMM_EINVAL, "more group entries than nodes: a node is in two groups");
+        if (n_in && !group_nodes) PHMM_THROW(PHMM_EINVAL, "NULL group_nodes");
+        // everything into temporaries: a refusal leaves the groups of the handle as they were
+        std::vector<uint32_t> g_of(N, NONE), g_cn(G, 0), g_emit(G, 0);
+        for (uint32_t g = 0; g < G; g++)
+            for (uint64_t i = group_off[g]; i < group_off[g + 1]; i++) {
+                const uint32_t v = group_nodes[i];
+                if (v >= N) PHMM_THROW(PHMM_EINVAL, "group node out of range");
+                if (g_of[v] != NONE) PHMM_THROW(PHMM_EINVAL, "node in two groups (or twice in one)");
+                g_of[v] = g;
+                if (i == group_off[g]) g_cn[g] = lk->cn[v];
+                else if (lk->cn[v] != g_cn[g])
+                    PHMM_THROW(PHMM_EINVAL, "the current copy numbers are not constant within group " + std::to_string(g));
+                if (lk->m->emission[v] != (uint8_t)'n') g_emit[g]++;
+            }
+        // boundary parents: parents of a group's nodes outside the group, one slot per distinct node
+        std::vector<uint2> slot(N);
+        for (uint32_t v = 0; v < N; v++) slot[v] = make_uint2(g_of[v], NONE);
+        std::vector<uint32_t> bp_off(G + 1, 0), bp_slot, slot_group;  // slot_group[p]: 1 + the last group that listed p
+        uint32_t P = 0;
+        for (uint32_t g = 0; g < G; g++) {
+            for (uint64_t i = group_off[g]; i < group_off[g + 1]; i++) {
+                const uint32_t v = group_nodes[i];
+                for (uint32_t q = lk->m->par_off[v]; q < lk->m->par_off[v + 1]; q++) {
+                    const uint32_t u = lk->m->par_node[q];
+                    if (g_of[u] == g) continue;
+                    if (slot[u].y == NONE) {
+                        slot[u].y = P++;
+                        slot_group.push_back(0);
+                    }
+                    if (slot_group[slot[u].y] == g + 1) continue;
+                    slot_group[slot[u].y] = g + 1;
+                    bp_slot.push_back(slot[u].y);
+                }
+            }
+            bp_off[g + 1] = (uint32_t)bp_slot.size();
+        }
+        if ((uint64_t)G + P >= NONE) PHMM_THROW(PHMM_EINVAL, "too many groups");
+        // from here only an allocation can fail; the handle is then left without groups
+        lk->G = 0;
+        lk->P = P;
+        lk->g_off.assign(group_off, group_off + (G ? G + 1 : 0));
+        if (!G) lk->g_off.assign(1, 0);
+        lk->g_nodes.assign(group_nodes, group_nodes + n_in);
+        lk->g_of.swap(g_of);
+        lk->g_cn.swap(g_cn);
+        lk->g_emit.swap(g_emit);
+        lk->g_seen.assign(G, 0u);
+        lk->g_at.assign(G, 0u);
+        lk->g_stamp = 0;
+        if (G) {
+            lk->d_g_off.upload(lk->g_off.data(), lk->g_off.size() * sizeof(uint64_t));
+            lk->d_g_nodes.upload(lk->g_nodes.data(), n_in * sizeof(uint32_t));
+            lk->d_g_slot.upload(slot.data(), (size_t)N * sizeof(uint2));
+            lk->d_bp_off.upload(bp_off.data(), bp_off.size() * sizeof(uint32_t));
+            lk->d_bp_slot.upload(bp_slot.data(), bp_slot.size() * sizeof(uint32_t));
+            HIP_CHECK(hipStreamSynchronize(current_stream()));  // (slot, bp_* are locals)
+        }
+        lk->G = G;
+    });
+}
+
+// a group change list names no group >= G, no group twice and no mixed group
+static void check_group_list(phmm_likelihood *lk, uint64_t j0, uint64_t j1, const uint32_t *group) {
+    if (++lk->g_stamp == 0) {
+        std::fill(lk->g_seen.begin(), lk->g_seen.end(), 0u);
+        lk->g_stamp = 1;
+    }
+    for (uint64_t j = j0; j < j1; j++) {
+        const uint32_t g = group[j];
+        if (g >= lk->G) PHMM_THROW(PHMM_EINVAL, "change group out of range");
+        if (lk->g_seen[g] == lk->g_stamp) PHMM_THROW(PHMM_EINVAL, "group listed twice in one change list");
+        if (lk->g_cn[g] == PHMM_GROUP_MIXED)
+            PHMM_THROW(PHMM_EINVAL, "group " + std::to_string(g) + " is mixed (a node-form move changed part of it)");
+        lk->g_seen[g] = lk->g_stamp;
+    }
+}
+
+int phmm_likelihood_score_group_changes(phmm_likelihood *lk, uint32_t n_cand, const uint64_t *change_off,
+                                        const uint32_t *change_group, const uint32_t *change_copy_num,
+                                        double *out_logp, double *out_total, uint64_t *out_n_rescored) {
+    if (!lk) return fail(PHMM_EINVAL, "NULL likelihood handle");
+    return guarded_on(lk->m, [&] {
+        if (!lk->G) PHMM_THROW(PHMM_EINVAL, "no groups set (phmm_likelihood_set_groups)");
+        if (n_cand == 0) return;
+        if (!change_off) PHMM_THROW(PHMM_EINVAL, "NULL change_off");
+        if (change_off[0] != 0) PHMM_THROW(PHMM_EINVAL, "change_off[0] must be 0");
+        for (uint32_t c = 0; c < n_cand; c++)
+            if (change_off[c + 1] < change_off[c]) PHMM_THROW(PHMM_EINVAL, "change_off decreases");
+        if (change_off[n_cand] && (!change_group || !change_copy_num)) PHMM_THROW(PHMM_EINVAL, "NULL change arrays");
+        for (uint32_t c = 0; c < n_cand; c++) check_group_list(lk, change_off[c], change_off[c + 1], change_group);
+        likelihood_score_changes(lk, n_cand, change_off, change_group, change_copy_num, out_logp, out_total,
+                                 out_n_rescored, true);
+    });
+}
+
+int phmm_likelihood_move_groups(phmm_likelihood *lk, uint64_t n_changes, const uint32_t *change_group,
+                                const uint32_t *change_copy_num, double *out_total, uint64_t *out_n_rescored) {
+    if (!lk) return fail(PHMM_EINVAL, "NULL likelihood handle");
+    return guarded_on(lk->m, [&] {
+        if (!lk->G) PHMM_THROW(PHMM_EINVAL, "no groups set (phmm_likelihood_set_groups)");
+        if (n_changes && (!change_group || !change_copy_num)) PHMM_THROW(PHMM_EINVAL, "NULL change arrays");
+        check_group_list(lk, 0, n_changes, change_group);
+        likelihood_move(lk, n_changes, change_group, change_copy_num, out_total, out_n_rescored, true);
+    });
+}
+
+int phmm_likelihood_current_groups(const phmm_likelihood *lk, uint32_t *out_group_copy_nums) {
+    if (!lk) return fail(PHMM_EINVAL, "NULL likelihood handle");
+    return guarded_on(lk->m, [&] {
+        if (!lk->G) PHMM_THROW(PHMM_EINVAL, "no groups set (phmm_likelihood_set_groups)");
+        if (!out_group_copy_nums) PHMM_THROW(PHMM_EINVAL, "NULL out_group_copy_nums");
+        std::memcpy(out_group_copy_nums, lk->g_cn.data(), (size_t)lk->G * sizeof(uint32_t));
+    });
+}
+
 void phmm_likelihood_destroy(phmm_likelihood *lk) { delete lk; }
 
 int phmm_mappings_map_nodes(phmm_model *model_after, const phmm_reads *reads, const phmm_mappings *mp,

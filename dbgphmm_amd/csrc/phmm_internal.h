@@ -332,6 +332,21 @@ struct phmm_likelihood {
     phmm::DevBuf d_cn, d_val, d_tat;    // u32[N], f64[R], u64[R]
     std::vector<uint32_t> seen;         // [N] stamp of the change list that last named the node
     uint32_t stamp = 0;
+    // Node groups (phmm_likelihood_set_groups): the k-mers of one compact edge, changed together.  Scoring in group
+    // units reads g_cn / g_emit only, never cn[]; the mask tables of a group-form call have G + P words per 64
+    // candidates, P = the distinct boundary parents over all groups (slot G + p).
+    uint32_t G = 0, P = 0;
+    std::vector<uint64_t> g_off;        // [G+1]
+    std::vector<uint32_t> g_nodes;      // [g_off[G]]
+    std::vector<uint32_t> g_of;         // [N] group of the node, PHMM_GROUP_MIXED (0xffffffff) for none
+    std::vector<uint32_t> g_cn;         // [G] current copy number, PHMM_GROUP_MIXED once a node-form move split it
+    std::vector<uint32_t> g_emit;       // [G] nodes with emission != 'n'
+    std::vector<uint32_t> g_seen;       // [G] stamps, as `seen`
+    std::vector<uint32_t> g_at;         // [G] scratch of a node-form move (index into its list of touched groups)
+    uint32_t g_stamp = 0;
+    // d_g_off u64[G+1], d_g_nodes u32[.], d_g_slot uint2[N] {group or none, boundary-parent slot or none},
+    // d_bp_off u32[G+1], d_bp_slot u32[.] boundary-parent slots per group
+    phmm::DevBuf d_g_off, d_g_nodes, d_g_slot, d_bp_off, d_bp_slot;
 };
 
 namespace phmm {
@@ -433,9 +448,10 @@ void full_prob_reads_copy_num_changes(phmm_model *m, const phmm_reads *reads, co
 // phmm_likelihood (sparse.hip): the same scoring against a vector and per-read values kept on the device
 void likelihood_refresh(phmm_likelihood *lk);  // also the first scoring of phmm_likelihood_create
 void likelihood_score_changes(phmm_likelihood *lk, uint32_t n_cand, const uint64_t *chg_off, const uint32_t *chg_node,
-                              const uint32_t *chg_cn, double *out_logp, double *out_total, uint64_t *out_n_rescored);
+                              const uint32_t *chg_cn, double *out_logp, double *out_total, uint64_t *out_n_rescored,
+                              bool by_group = false);  // by_group: chg_node holds group ids (phmm_likelihood_set_groups)
 void likelihood_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_node, const uint32_t *chg_cn,
-                     double *out_total, uint64_t *out_n_rescored);
+                     double *out_total, uint64_t *out_n_rescored, bool by_group = false);
 void likelihood_current(const phmm_likelihood *lk, uint32_t *out_cn, double *out_logp, double *out_total);
 void upload_reads(const phmm_reads *r);
 void upload_mappings(const phmm_mappings *mp);

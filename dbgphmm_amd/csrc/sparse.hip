@@ -1143,6 +1143,39 @@ __global__ void __launch_bounds__(256) cnc_read_mask(const uint64_t *read_off, u
     for (int off = 32; off >= 1; off >>= 1) acc |= __shfl_xor(acc, off);
     if ((threadIdx.x & 63) == 0) read_mask[(size_t)blockIdx.y * R + r] = acc;
 }
+// Group flavours (phmm_likelihood_set_groups): the mask table of one word has S = G + P entries, a word per group and
+// a word per distinct boundary parent (a parent of a node of some group that is not in that group), instead of N.
+// bit c % 64 of word c / 64 in the entry of g and of each boundary parent of g, per effective change {c, g}
+__global__ void __launch_bounds__(256) cng_mark(const uint2 *chg, uint32_t n_chg, const uint32_t *bp_off,
+                                                const uint32_t *bp_slot, uint32_t G, uint32_t S,
+                                                unsigned long long *slot_mask) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_chg) return;
+    const uint32_t c = chg[j].x, g = chg[j].y;
+    const unsigned long long bit = 1ull << (c & 63);
+    unsigned long long *w = slot_mask + (size_t)(c >> 6) * S;
+    atomicOr(&w[g], bit);
+    for (uint32_t q = bp_off[g]; q < bp_off[g + 1]; q++) atomicOr(&w[G + bp_slot[q]], bit);
+}
+// cnc_read_mask over that table: per list entry v the word of its group and its own word as a boundary parent
+// (node_slot[v] = {group, boundary-parent slot}, 0xffffffff for none) -- A_c = D_c + parents(D_c), as the node form
+__global__ void __launch_bounds__(256) cng_read_mask(const uint64_t *read_off, uint64_t R, const uint64_t *map_pos_off,
+                                                     const uint32_t *map_nodes, const uint2 *node_slot, uint32_t G,
+                                                     uint32_t S, const unsigned long long *slot_mask,
+                                                     unsigned long long *read_mask) {
+    const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const unsigned long long *w = slot_mask + (size_t)blockIdx.y * S;
+    const uint64_t e0 = map_pos_off[read_off[r]], e1 = map_pos_off[read_off[r + 1]];
+    unsigned long long acc = 0;
+    for (uint64_t e = e0 + (threadIdx.x & 63); e < e1; e += 64) {
+        const uint2 sl = node_slot[map_nodes[e]];
+        if (sl.x != 0xffffffffu) acc |= w[sl.x];
+        if (sl.y != 0xffffffffu) acc |= w[G + sl.y];
+    }
+    for (int off = 32; off >= 1; off >>= 1) acc |= __shfl_xor(acc, off);
+    if ((threadIdx.x & 63) == 0) read_mask[(size_t)blockIdx.y * R + r] = acc;
+}
 // copy-number vectors of the D candidates with a dirty read: the base, then their changes {slot, node, cn}
 __global__ void __launch_bounds__(256) cnc_expand(const uint32_t *base, uint32_t N, uint32_t *cn) {
     const uint32_t v = blockIdx.x * 256 + threadIdx.x;
@@ -1151,6 +1184,13 @@ __global__ void __launch_bounds__(256) cnc_expand(const uint32_t *base, uint32_t
 __global__ void __launch_bounds__(256) cnc_apply(const uint3 *chg, uint32_t n_chg, uint32_t N, uint32_t *cn) {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j < n_chg) cn[(size_t)chg[j].x * N + chg[j].y] = chg[j].z;
+}
+// changes {slot, group, cn}: a block per change writes cn over the group's nodes
+__global__ void __launch_bounds__(256) cng_apply(const uint3 *chg, const uint64_t *g_off, const uint32_t *g_nodes,
+                                                 uint32_t N, uint32_t *cn) {
+    const uint3 t = chg[blockIdx.x];
+    uint32_t *o = cn + (size_t)t.x * N;
+    for (uint64_t i = g_off[t.y] + threadIdx.x; i < g_off[t.y + 1]; i += 256) o[g_nodes[i]] = t.z;
 }
 // results of the pairs {read, slot} out of the [D][R] planes the scoring kernels write
 __global__ void __launch_bounds__(256) cnc_gather(const uint2 *pairs, size_t n, uint64_t R, const double *out,
@@ -1184,6 +1224,7 @@ struct CncJob {
     uint32_t min_cn = 0, C = 0;
     const uint64_t *chg_off = nullptr;
     const uint32_t *chg_node = nullptr, *chg_cn = nullptr;
+    const phmm_likelihood *grp = nullptr;  // chg_node holds group ids of this handle (uniform groups, checked by the caller)
     bool on_device = false;  // keep the read masks (aux[13]) and every final value in the [D][R] planes (aux[11])
     // out
     std::vector<uint8_t> full;       // [C] no finite shift: every non-empty read is rescored
@@ -1206,9 +1247,13 @@ void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, 
     const uint32_t *chg_node = job.chg_node, *chg_cn = job.chg_cn;
     const uint64_t Tb = job.Tb;
     auto eff = [&](uint32_t k) { return std::max(k, min_cn); };
+    const phmm_likelihood *grp = job.grp;
+    const uint32_t G = grp ? grp->G : 0;
+    const size_t S = grp ? (size_t)G + grp->P : N;  // entries of one word of the mask table
 
-    // effective changes (e differs from the base) and T_c, exact in integers
-    std::vector<uint2> marks;  // {candidate, node}
+    // effective changes (e differs from the base) and T_c, exact in integers; in group units from the group table
+    // alone: every node of a group holds g_cn, so d is the node form's d and the group adds d per emittable node
+    std::vector<uint2> marks;  // {candidate, node or group}
     std::vector<uint8_t> &full = job.full;
     std::vector<double> &shift = job.shift;
     full.assign(C, 0);
@@ -1218,6 +1263,13 @@ void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, 
         int64_t dT = 0;
         for (uint64_t j = chg_off[c]; j < chg_off[c + 1]; j++) {
             const uint32_t v = chg_node[j];
+            if (grp) {
+                const int64_t d = (int64_t)eff(chg_cn[j]) - (int64_t)eff(grp->g_cn[v]);
+                if (d == 0 || grp->g_off[v + 1] == grp->g_off[v]) continue;
+                marks.push_back(make_uint2(c, v));
+                dT += d * (int64_t)grp->g_emit[v];
+                continue;
+            }
             const int64_t d = (int64_t)eff(chg_cn[j]) - (int64_t)eff(base_cn[v]);
             if (d == 0) continue;
             marks.push_back(make_uint2(c, v));
@@ -1237,22 +1289,31 @@ void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, 
     DevBuf &d_mask = m->wset().aux[22], &d_list = m->wset().aux[23];
     DevBuf &d_nrmask = job.on_device ? m->wset().aux[13] : d_mask;  // (d_mask takes the pairs below)
     if (job.on_device) {
-        d_nrmask.reserve((size_t)W * N * 8 + (size_t)W * R * 8);
-        unsigned long long *rm = d_nrmask.as<unsigned long long>() + (size_t)W * N;
+        d_nrmask.reserve((size_t)W * S * 8 + (size_t)W * R * 8);
+        unsigned long long *rm = d_nrmask.as<unsigned long long>() + (size_t)W * S;
         if (marks.empty()) HIP_CHECK(hipMemsetAsync(rm, 0, (size_t)W * R * 8, s));
         job.d_rmask = rm;
     }
     if (!marks.empty()) {
-        const size_t nm_bytes = (size_t)W * N * 8, rm_bytes = (size_t)W * R * 8;
+        const size_t nm_bytes = (size_t)W * S * 8, rm_bytes = (size_t)W * R * 8;
         d_nrmask.reserve(nm_bytes + rm_bytes);
         d_list.reserve(marks.size() * sizeof(uint2));
-        unsigned long long *nm = d_nrmask.as<unsigned long long>(), *rm = nm + (size_t)W * N;
+        unsigned long long *nm = d_nrmask.as<unsigned long long>(), *rm = nm + (size_t)W * S;
         HIP_CHECK(hipMemsetAsync(nm, 0, nm_bytes, s));
         HIP_CHECK(hipMemcpyAsync(d_list.p, marks.data(), marks.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(cnc_mark, dim3((unsigned)((marks.size() + 255) / 256)), dim3(256), 0, s, d_list.as<uint2>(),
-                           (uint32_t)marks.size(), m->dev.par_off.as<uint32_t>(), m->dev.par_node.as<uint32_t>(), N, nm);
-        hipLaunchKernelGGL(cnc_read_mask, dim3((unsigned)((R + 3) / 4), W), dim3(256), 0, s, reads->d_off.as<uint64_t>(), R,
-                           mp->d_pos_off.as<uint64_t>(), mp->d_nodes.as<uint32_t>(), N, nm, rm);
+        if (grp) {
+            hipLaunchKernelGGL(cng_mark, dim3((unsigned)((marks.size() + 255) / 256)), dim3(256), 0, s, d_list.as<uint2>(),
+                               (uint32_t)marks.size(), grp->d_bp_off.as<uint32_t>(), grp->d_bp_slot.as<uint32_t>(), G,
+                               (uint32_t)S, nm);
+            hipLaunchKernelGGL(cng_read_mask, dim3((unsigned)((R + 3) / 4), W), dim3(256), 0, s,
+                               reads->d_off.as<uint64_t>(), R, mp->d_pos_off.as<uint64_t>(), mp->d_nodes.as<uint32_t>(),
+                               grp->d_g_slot.as<uint2>(), G, (uint32_t)S, (const unsigned long long *)nm, rm);
+        } else {
+            hipLaunchKernelGGL(cnc_mark, dim3((unsigned)((marks.size() + 255) / 256)), dim3(256), 0, s, d_list.as<uint2>(),
+                               (uint32_t)marks.size(), m->dev.par_off.as<uint32_t>(), m->dev.par_node.as<uint32_t>(), N, nm);
+            hipLaunchKernelGGL(cnc_read_mask, dim3((unsigned)((R + 3) / 4), W), dim3(256), 0, s, reads->d_off.as<uint64_t>(),
+                               R, mp->d_pos_off.as<uint64_t>(), mp->d_nodes.as<uint32_t>(), N, nm, rm);
+        }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(rmask.data(), rm, rm_bytes, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
@@ -1324,7 +1385,10 @@ void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, 
         HIP_CHECK(hipMemsetAsync(d_tot, 0, D * sizeof(unsigned long long), s));
         const unsigned nb = (unsigned)((N + 255) / 256);
         hipLaunchKernelGGL(cnc_expand, dim3(nb, D), dim3(256), 0, s, d_base, N, d_cn);
-        if (!apply.empty())
+        if (!apply.empty() && grp)  // {slot, group, cn}
+            hipLaunchKernelGGL(cng_apply, dim3((unsigned)apply.size()), dim3(256), 0, s, (const uint3 *)d_apply,
+                               grp->d_g_off.as<uint64_t>(), grp->d_g_nodes.as<uint32_t>(), N, d_cn);
+        else if (!apply.empty())
             hipLaunchKernelGGL(cnc_apply, dim3((unsigned)((apply.size() + 255) / 256)), dim3(256), 0, s,
                                (const uint3 *)d_apply, (uint32_t)apply.size(), N, d_cn);
         hipLaunchKernelGGL(cn_totals, dim3(std::min(nb, 256u), D), dim3(256), 0, s, (const uint32_t *)d_cn,
@@ -1672,7 +1736,8 @@ void likelihood_refresh(phmm_likelihood *lk) {
 }
 
 void likelihood_score_changes(phmm_likelihood *lk, uint32_t C, const uint64_t *chg_off, const uint32_t *chg_node,
-                              const uint32_t *chg_cn, double *out_logp, double *out_total, uint64_t *out_n_rescored) {
+                              const uint32_t *chg_cn, double *out_logp, double *out_total, uint64_t *out_n_rescored,
+                              bool by_group) {
     const uint64_t R = lk->reads->R;
     if (R == 0) {
         const std::vector<double> z(C, 0.0);
@@ -1692,6 +1757,7 @@ void likelihood_score_changes(phmm_likelihood *lk, uint32_t C, const uint64_t *c
     job.chg_off = chg_off;
     job.chg_node = chg_node;
     job.chg_cn = chg_cn;
+    job.grp = by_group ? lk : nullptr;
     job.on_device = true;
     cnc_score(lk->m, lk->reads, lk->mp, job);
 
@@ -1704,8 +1770,42 @@ void likelihood_score_changes(phmm_likelihood *lk, uint32_t C, const uint64_t *c
     trace("lk: compose (device)");
 }
 
+namespace {
+// a node-form move of nodes that lie in groups: a group all of whose nodes took one value follows it, a group whose
+// changed nodes keep its value is untouched, any other becomes mixed.  O(changes).
+void lk_groups_after_node_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_node, const uint32_t *chg_cn) {
+    if (!lk->G) return;
+    struct Touch {
+        uint32_t g, n, val;
+        bool one_val;
+    };
+    std::vector<Touch> touched;
+    if (++lk->g_stamp == 0) {
+        std::fill(lk->g_seen.begin(), lk->g_seen.end(), 0u);
+        lk->g_stamp = 1;
+    }
+    std::vector<uint32_t> &at = lk->g_at;
+    for (uint64_t j = 0; j < n_chg; j++) {
+        const uint32_t g = lk->g_of[chg_node[j]];
+        if (g == 0xffffffffu) continue;
+        if (lk->g_seen[g] != lk->g_stamp) {
+            lk->g_seen[g] = lk->g_stamp;
+            at[g] = (uint32_t)touched.size();
+            touched.push_back(Touch{g, 0, chg_cn[j], true});
+        }
+        Touch &t = touched[at[g]];
+        t.n++;
+        t.one_val = t.one_val && chg_cn[j] == t.val;
+    }
+    for (const Touch &t : touched) {
+        if (t.one_val && t.n == lk->g_off[t.g + 1] - lk->g_off[t.g]) lk->g_cn[t.g] = t.val;
+        else if (!(t.one_val && t.val == lk->g_cn[t.g])) lk->g_cn[t.g] = 0xffffffffu;
+    }
+}
+}  // namespace
+
 void likelihood_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_node, const uint32_t *chg_cn,
-                     double *out_total, uint64_t *out_n_rescored) {
+                     double *out_total, uint64_t *out_n_rescored, bool by_group) {
     hipStream_t s = current_stream();
     const uint64_t R = lk->reads->R;
     const uint32_t N = lk->m->N;
@@ -1721,6 +1821,7 @@ void likelihood_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_no
         job.chg_off = off;
         job.chg_node = chg_node;
         job.chg_cn = chg_cn;
+        job.grp = by_group ? lk : nullptr;
         job.on_device = true;
         uint64_t T_new = 0;
         if (R) {
@@ -1731,7 +1832,10 @@ void likelihood_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_no
         } else {
             int64_t dT = 0;
             for (uint64_t j = 0; j < n_chg; j++)
-                if (lk->m->emission[chg_node[j]] != (uint8_t)'n')
+                if (by_group)
+                    dT += ((int64_t)std::max(chg_cn[j], lk->min_cn) - (int64_t)std::max(lk->g_cn[chg_node[j]], lk->min_cn)) *
+                          (int64_t)lk->g_emit[chg_node[j]];
+                else if (lk->m->emission[chg_node[j]] != (uint8_t)'n')
                     dT += (int64_t)std::max(chg_cn[j], lk->min_cn) - (int64_t)std::max(lk->cn[chg_node[j]], lk->min_cn);
             T_new = (uint64_t)((int64_t)lk->T + dT);
         }
@@ -1756,11 +1860,24 @@ void likelihood_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_no
                                lk->reads->d_off.as<uint64_t>(), R, job.d_rmask, (uint32_t)job.full[0],
                                (const double *)lk->m->wset().aux[11].as<double>(), (unsigned long long)T_new,
                                lk->d_val.as<double>(), lk->d_tat.as<unsigned long long>());
-        hipLaunchKernelGGL(cnc_apply, dim3((unsigned)((apply.size() + 255) / 256)), dim3(256), 0, s,
-                           (const uint3 *)d_apply.as<uint3>(), (uint32_t)apply.size(), N, lk->d_cn.as<uint32_t>());
+        if (by_group)
+            hipLaunchKernelGGL(cng_apply, dim3((unsigned)apply.size()), dim3(256), 0, s, (const uint3 *)d_apply.as<uint3>(),
+                               lk->d_g_off.as<uint64_t>(), lk->d_g_nodes.as<uint32_t>(), N, lk->d_cn.as<uint32_t>());
+        else
+            hipLaunchKernelGGL(cnc_apply, dim3((unsigned)((apply.size() + 255) / 256)), dim3(256), 0, s,
+                               (const uint3 *)d_apply.as<uint3>(), (uint32_t)apply.size(), N, lk->d_cn.as<uint32_t>());
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));
-        for (uint64_t j = 0; j < n_chg; j++) lk->cn[chg_node[j]] = chg_cn[j];
+        if (by_group) {  // (the host mirror is written here only: scoring in group units reads g_cn)
+            for (uint64_t j = 0; j < n_chg; j++) {
+                const uint32_t g = chg_node[j];
+                for (uint64_t i = lk->g_off[g]; i < lk->g_off[g + 1]; i++) lk->cn[lk->g_nodes[i]] = chg_cn[j];
+                lk->g_cn[g] = chg_cn[j];
+            }
+        } else {
+            lk_groups_after_node_move(lk, n_chg, chg_node, chg_cn);
+            for (uint64_t j = 0; j < n_chg; j++) lk->cn[chg_node[j]] = chg_cn[j];
+        }
         lk->T = T_new;
         put_doubles(out_total, &total, 1);
     } else if (out_total) {

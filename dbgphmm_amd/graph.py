@@ -222,6 +222,39 @@ def toy_repeat() -> Tuple[SeqGraph, int]:
     return node_centric_from_dbg(term, edges), 4
 
 
+def unitig_groups(sg: SeqGraph) -> Tuple[np.ndarray, np.ndarray]:
+    """The node groups of Likelihood.set_groups for a test or timing graph: every node in exactly one group, a group
+    being a maximal path v1 -> ... -> vn in which each step a -> b has out-degree(a) = 1, in-degree(b) = 1 and equal
+    copy numbers, nodes in path order; a cycle without a branch is one group cut at its smallest node id.  Groups are
+    ordered by their first node, cycles last.  -> (group_off[G+1] uint64, group_nodes[N] uint32).  (The sampler
+    itself passes MultiDbg::edges_in_full of its compact edges, multi_dbg.rs:1041-1052.)"""
+    n = sg.base.shape[0]
+    src, dst = sg.edge_src.astype(np.int64), sg.edge_dst.astype(np.int64)
+    outdeg, indeg = np.bincount(src, minlength=n), np.bincount(dst, minlength=n)
+    step = (outdeg[src] == 1) & (indeg[dst] == 1) & (sg.copy_num[src] == sg.copy_num[dst])
+    nxt, prv = np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64)
+    nxt[src[step]] = dst[step]
+    prv[dst[step]] = src[step]
+    nodes = np.empty(n, dtype=np.uint32)
+    off = [0]
+    done = np.zeros(n, dtype=bool)
+    nxt_l = nxt.tolist()
+    fill = 0
+    # paths from their heads, then what is left: cycles all of whose steps qualify, from their smallest node
+    for heads in (np.flatnonzero(prv < 0).tolist(), None):
+        for v in (heads if heads is not None else np.flatnonzero(~done).tolist()):
+            if done[v]:
+                continue
+            while v >= 0 and not done[v]:
+                done[v] = True
+                nodes[fill] = v
+                fill += 1
+                v = nxt_l[v]
+            off.append(fill)
+    assert fill == n
+    return np.array(off, dtype=np.uint64), nodes
+
+
 # ---------------------------------------------------------------- synthetic genomes / DBG
 
 _B = np.uint64(0x9E3779B97F4A7C15)  # odd multiplier for the rolling hash

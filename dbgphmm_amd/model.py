@@ -418,6 +418,58 @@ class Likelihood:
         """Rescore the current vector in full (after PHMMModel.set_params)."""
         _ffi.check(_ffi.lib().phmm_likelihood_refresh(self._h))
 
+    # ---- the same calls in the sampler's own units: node groups = the k-mers of one compact edge
+    def set_groups(self, group_off, group_nodes) -> None:
+        """Groups of nodes the sampler changes together: group g = group_nodes[group_off[g]:group_off[g+1]], the
+        k-mers of one compact edge (MultiDbg::edges_in_full; set_copy_nums writes one compact edge's copy number
+        into every k-mer of its unitig, multi_dbg.rs:1041-1052).  Disjoint; the current vector must be constant
+        within each.  Replaces earlier groups; an empty group_off removes them.  graph.unitig_groups builds them for
+        a SeqGraph."""
+        off = np.ascontiguousarray(group_off, dtype=np.uint64).reshape(-1)
+        nodes = np.ascontiguousarray(group_nodes, dtype=np.uint32).reshape(-1)
+        n_groups = max(off.size - 1, 0)
+        if n_groups and int(off[-1]) != nodes.size:
+            raise ValueError("group_off[-1] must be len(group_nodes)")
+        _ffi.check(_ffi.lib().phmm_likelihood_set_groups(self._h, n_groups, _ptr(off), _ptr(nodes)))
+        self.n_groups = n_groups
+
+    def score_group_changes(self, changes, out_logp=None, per_read: bool = True):
+        """score_changes with changes = (off[C+1], group, cn) in group units: the neighbours of sample_posterior_once
+        (posterior.rs:470-528) as UpdateInfo::cycle() states them, +1 / -1 on compact edges -- bit for bit what
+        score_changes returns for the lists expanded to nodes -> (totals[C], per_read[C,R] or None, n_rescored[C])."""
+        off, group, cn = changes
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        group = np.ascontiguousarray(group, dtype=np.uint32)
+        cn = np.ascontiguousarray(cn, dtype=np.uint32)
+        Cn = off.size - 1
+        lp = out_logp if out_logp is not None else (np.empty((Cn, len(self.reads))) if per_read else None)
+        tot = np.empty(Cn)
+        nr = np.empty(Cn, dtype=np.uint64)
+        _ffi.check(_ffi.lib().phmm_likelihood_score_group_changes(self._h, Cn, _ptr(off), _ptr(group), _ptr(cn),
+                                                                  _ptr(lp), _ptr(tot), _ptr(nr)))
+        return tot, lp, nr
+
+    def move_groups(self, groups, copy_nums):
+        """move in group units: every node of groups[j] takes copy_nums[j] (posterior.rs:532-600; set_copy_nums,
+        multi_dbg.rs:1041-1052) -> (ln P(R | new vector), reads rescored)."""
+        group = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        cn = np.ascontiguousarray(copy_nums, dtype=np.uint32).reshape(-1)
+        if group.size != cn.size:
+            raise ValueError("groups and copy_nums differ in length")
+        tot = np.empty(1)
+        nr = np.empty(1, dtype=np.uint64)
+        _ffi.check(_ffi.lib().phmm_likelihood_move_groups(self._h, group.size, _ptr(group), _ptr(cn), _ptr(tot),
+                                                          _ptr(nr)))
+        return float(tot[0]), int(nr[0])
+
+    def current_groups(self) -> np.ndarray:
+        """The current vector in group units, as get_copy_nums returns it over compact edges (PosteriorSample.copy_nums,
+        posterior.rs:314-417; multi_dbg.rs:1041-1052 is its inverse) -> uint32[G], _ffi.PHMM_GROUP_MIXED for a group
+        a node-form move has split."""
+        out = np.empty(getattr(self, "n_groups", 0), dtype=np.uint32)
+        _ffi.check(_ffi.lib().phmm_likelihood_current_groups(self._h, _ptr(out)))
+        return out
+
 
 class PHMMOutput:
     """PHMMOutput (src/hmmv2/table.rs:450-517) of one dense run."""

@@ -273,8 +273,46 @@ int phmm_likelihood_move(phmm_likelihood *lk, uint64_t n_changes, const uint32_t
 /* What the handle holds: copy_nums[N] (host), per-read ln P [R], their sum (host or device).  Any may be NULL. */
 int phmm_likelihood_current(const phmm_likelihood *lk, uint32_t *out_copy_nums, double *out_logp, double *out_total);
 
-/* Rescores the current vector in full (after phmm_model_set_params, or to drop the one rounding of shifted reads). */
+/* Rescores the current vector in full (after phmm_model_set_params, or to drop the one rounding of shifted reads).
+ * Does not touch the groups. */
 int phmm_likelihood_refresh(phmm_likelihood *lk);
+
+/* ---- the handle in the sampler's own units: node groups ---------------------------
+ * The sampler's state is a copy-number vector over COMPACT edges (get_copy_nums, CopyNums; UpdateInfo::cycle(),
+ * neighbors.rs:193-216), and set_copy_nums writes one compact edge's number into every k-mer of its unitig
+ * (multi_dbg.rs:1041-1052).  A group is the node set of one compact edge; the group forms below take and return
+ * compact-edge numbers, so that the work in front of the scoring kernels scales with the number of GROUP changes,
+ * not with k.
+ * Equality with the node form: a group change (g, cn) means (v, cn) for every node v of g.  For any handle state and
+ * any group change lists, score_group_changes / move_groups write exactly what score_changes / move write for the
+ * expanded lists -- out_logp, out_total, out_n_rescored with the same bits, the same reads rescored -- and after a
+ * move the handle is in the same state (phmm_likelihood_current returns the same vector, per-read values and total).
+ * Uniform groups: set_groups requires the current vector to be constant within every group.  A later node-form
+ * phmm_likelihood_move may change part of a group: that group is then MIXED -- a group-form call that names it is
+ * refused, phmm_likelihood_current_groups reports PHMM_GROUP_MIXED for it, every other group keeps working, and
+ * phmm_likelihood_set_groups re-validates.  (A node-form move that gives every node of a group one value leaves it
+ * uniform at that value.)
+ * Refusals are PHMM_EINVAL, write no output and leave vector, T, per-read values and groups as they were: NULL handle
+ * or arrays, group_off not starting at 0 or decreasing, a node id >= N, a node in two groups (or twice in one), a
+ * group id >= G, a group named twice within one candidate or move, a group-form call with no groups set, a mixed
+ * group named.  Empty groups are allowed and are never effective.  Groups belong to the handle and die with it. */
+#define PHMM_GROUP_MIXED 0xffffffffu
+
+/* Groups = disjoint sets of PHMM nodes that the sampler changes together: the k-mers of one compact edge
+ * (MultiDbg::edges_in_full).  group_off[G+1], group_nodes[group_off[G]], host pointers.  A node may be in no group
+ * (it can then only be changed through the node form).  Replaces any earlier groups; n_groups = 0 removes them. */
+int phmm_likelihood_set_groups(phmm_likelihood *lk, uint32_t n_groups, const uint64_t *group_off,
+                               const uint32_t *group_nodes);
+/* phmm_likelihood_score_changes with change_group[] (group ids) in place of change_node[]; outputs NULL, host or
+ * device as there; n_candidates = 0 writes nothing. */
+int phmm_likelihood_score_group_changes(phmm_likelihood *lk, uint32_t n_candidates, const uint64_t *change_off,
+                                        const uint32_t *change_group, const uint32_t *change_copy_num,
+                                        double *out_logp, double *out_total, uint64_t *out_n_rescored);
+/* phmm_likelihood_move with group ids; n_changes = 0 changes nothing. */
+int phmm_likelihood_move_groups(phmm_likelihood *lk, uint64_t n_changes, const uint32_t *change_group,
+                                const uint32_t *change_copy_num, double *out_total, uint64_t *out_n_rescored);
+/* the current vector in group units: out_group_copy_nums[G] (host), PHMM_GROUP_MIXED for a mixed group */
+int phmm_likelihood_current_groups(const phmm_likelihood *lk, uint32_t *out_group_copy_nums);
 void phmm_likelihood_destroy(phmm_likelihood *lk);
 
 /* PHMMModel::to_full_prob_sparse_backward (freq.rs:153-163): ln P(read) from PHMMModel::backward_sparse

@@ -15,9 +15,11 @@ use super::common::{PHMMEdge, PHMMModel, PHMMNode};
 use super::hint::{Mapping, Mappings};
 use super::params::PHMMParams;
 use crate::common::collection::ReadCollection;
-use crate::common::Seq;
+use crate::common::{CopyNum, Seq};
+use crate::multi_dbg::neighbors::UpdateInfo;
+use crate::multi_dbg::{CopyNums, MultiDbg};
 use crate::prob::Prob;
-use petgraph::graph::NodeIndex;
+use petgraph::graph::{EdgeIndex, NodeIndex};
 use std::ffi::CStr;
 use std::os::raw::c_int;
 use std::ptr;
@@ -391,5 +393,71 @@ impl AmdLikelihood {
             phmm_likelihood_move(self.state, node.len() as u64, node.as_ptr(), cn.as_ptr(), &mut total, ptr::null_mut())
         });
         Prob::from_log_prob(total)
+    }
+    // ---- the same search in the sampler's own units: compact edges (node groups of the handle)
+    /// After begin(): group g = the k-mers of compact edge g (MultiDbg::edges_in_full; PHMM node id = full-edge id,
+    /// multi_dbg.rs:1569-1576), so that neighbours and moves are stated as the sampler holds them -- copy numbers of
+    /// compact edges -- and set_copy_nums' loop over every k-mer of a unitig (multi_dbg.rs:1041-1052) runs on the
+    /// device.  Once per k.
+    pub fn set_compact_edges(&mut self, dbg: &MultiDbg) {
+        assert!(!self.state.is_null());
+        let mut off: Vec<u64> = Vec::with_capacity(dbg.n_edges_compact() + 1);
+        let mut nodes: Vec<u32> = Vec::with_capacity(self.n_nodes);
+        off.push(0);
+        for e in 0..dbg.n_edges_compact() {
+            nodes.extend(dbg.edges_in_full(EdgeIndex::new(e)).iter().map(|f| f.index() as u32));
+            off.push(nodes.len() as u64);
+        }
+        check(unsafe { phmm_likelihood_set_groups(self.state, (off.len() - 1) as u32, off.as_ptr(), nodes.as_ptr()) });
+    }
+    /// sample_posterior_once (posterior.rs:470-528) on the neighbours as to_neighbor_copy_nums_and_infos returns
+    /// them: neighbour c changes the compact edges of its UpdateInfo cycles (neighbors.rs:193-216) to the numbers its
+    /// CopyNums holds there.  No edges_in_full loop -> (ln P(R | X_c), reads rescored).
+    pub fn likelihoods_of_compact_neighbors(&mut self, neighbors: &[(CopyNums, UpdateInfo)]) -> (Vec<Prob>, Vec<u64>) {
+        assert!(!self.state.is_null());
+        let (mut off, mut edge, mut cn) = (vec![0u64], Vec::<u32>::new(), Vec::<u32>::new());
+        for (copy_nums, info) in neighbors {
+            let from = edge.len();
+            for cycle in &info.cycles {  // (one cycle, or the cycles of a MultiMove)
+                for (e, _dir) in cycle.iter() {
+                    if !edge[from..].contains(&(e.index() as u32)) {  // (a cycle may pass an edge twice)
+                        edge.push(e.index() as u32);
+                        cn.push(copy_nums[*e] as u32);
+                    }
+                }
+            }
+            off.push(edge.len() as u64);
+        }
+        let c = off.len() - 1;
+        let mut totals = vec![0f64; c];
+        let mut rescored = vec![0u64; c];
+        check(unsafe {
+            phmm_likelihood_score_group_changes(self.state, c as u32, off.as_ptr(), edge.as_ptr(), cn.as_ptr(),
+                                                ptr::null_mut(), totals.as_mut_ptr(), rescored.as_mut_ptr())
+        });
+        (totals.into_iter().map(Prob::from_log_prob).collect(), rescored)
+    }
+    /// The move (posterior.rs:532-590) in compact-edge units: every k-mer of edge[j] takes cn[j] -> ln P(R | new vector).
+    pub fn accept_compact(&mut self, edge: &[u32], cn: &[u32]) -> Prob {
+        assert!(!self.state.is_null() && edge.len() == cn.len());
+        let mut total = 0f64;
+        check(unsafe {
+            phmm_likelihood_move_groups(self.state, edge.len() as u64, edge.as_ptr(), cn.as_ptr(), &mut total,
+                                        ptr::null_mut())
+        });
+        Prob::from_log_prob(total)
+    }
+    /// The current vector over compact edges, as get_copy_nums returns it (multi_dbg.rs:1056-1062): what a
+    /// PosteriorSample.copy_nums holds.
+    pub fn copy_nums_compact(&self, dbg: &MultiDbg) -> CopyNums {
+        assert!(!self.state.is_null());
+        let mut g = vec![0u32; dbg.n_edges_compact()];
+        check(unsafe { phmm_likelihood_current_groups(self.state, g.as_mut_ptr()) });
+        let mut out = CopyNums::new(g.len(), 0);
+        for (e, v) in g.iter().enumerate() {
+            assert!(*v != PHMM_GROUP_MIXED);  // (only a node-form accept() on part of a unitig can do that)
+            out[EdgeIndex::new(e)] = *v as CopyNum;
+        }
+        out
     }
 }

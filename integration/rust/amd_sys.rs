@@ -62,6 +62,9 @@ pub struct phmm_likelihood {
 }
 
 #[link(name = "phmm_amd")]
+/// phmm_likelihood_current_groups: a node-form move changed part of the group
+pub const PHMM_GROUP_MIXED: u32 = 0xffff_ffff;
+
 extern "C" {
     pub fn phmm_last_error() -> *const c_char;
     pub fn phmm_version() -> *const c_char;
@@ -134,6 +137,16 @@ extern "C" {
                                    out_total: *mut f64) -> c_int;
     pub fn phmm_likelihood_refresh(lk: *mut phmm_likelihood) -> c_int;
     pub fn phmm_likelihood_destroy(lk: *mut phmm_likelihood);
+    pub fn phmm_likelihood_set_groups(lk: *mut phmm_likelihood, n_groups: u32, group_off: *const u64,
+                                      group_nodes: *const u32) -> c_int;
+    pub fn phmm_likelihood_score_group_changes(lk: *mut phmm_likelihood, n_candidates: u32, change_off: *const u64,
+                                               change_group: *const u32, change_copy_num: *const u32,
+                                               out_logp: *mut f64, out_total: *mut f64, out_n_rescored: *mut u64)
+                                               -> c_int;
+    pub fn phmm_likelihood_move_groups(lk: *mut phmm_likelihood, n_changes: u64, change_group: *const u32,
+                                       change_copy_num: *const u32, out_total: *mut f64, out_n_rescored: *mut u64)
+                                       -> c_int;
+    pub fn phmm_likelihood_current_groups(lk: *const phmm_likelihood, out_group_copy_nums: *mut u32) -> c_int;
     pub fn phmm_full_prob_sparse_backward(m: *mut phmm_model, reads: *const phmm_reads, out_logp: *mut f64,
                                           out_total: *mut f64) -> c_int;
     pub fn phmm_run_sparse(m: *mut phmm_model, reads: *const phmm_reads, out_logp_forward: *mut f64,
