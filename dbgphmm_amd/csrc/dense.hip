@@ -995,7 +995,9 @@ __global__ void __launch_bounds__(BLOCK) to_log_tables(const double *T, const in
     if (idx >= (size_t)L * N) return;
     const int pos = (int)(idx / N);
     const double v = T[idx];
-    out[idx] = v > 0.0 ? log(v) + (double)E[pos] * LN2 : -INFINITY;
+    // A denormal cell (~708 .. 745 nats below the column's scale) keeps only a few bits: reported as flushed, like the
+    // cells below it, not as a finite value that is wrong by up to a factor of 2.
+    out[idx] = v >= 2.2250738585072014e-308 ? log(v) + (double)E[pos] * LN2 : -INFINITY;
 }
 
 // ------------------------------------------------------------------ host driver
