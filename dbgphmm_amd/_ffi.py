@@ -12,6 +12,9 @@ CSRC = os.path.join(_HERE, "csrc")
 
 PHMM_OK, PHMM_EINVAL, PHMM_ENODEVICE, PHMM_ENOMEM, PHMM_ECAPACITY, PHMM_EINTERNAL = 0, -1, -2, -3, -4, -5
 PHMM_GROUP_MIXED = 0xFFFFFFFF  # phmm_likelihood_current_groups: a node-form move changed part of the group
+# phmm_last_call_stats classes: dense forward / dense backward + posterior / hinted + sparse forward / sparse backward /
+# the wide class of the hinted forward (mapping lists of 65-400 nodes; part of class 2 as well; opt-in: PHMM_WIDE_HINTED=1)
+PHMM_STATS_DENSE_FWD, PHMM_STATS_DENSE_BWD, PHMM_STATS_SPARSE_FWD, PHMM_STATS_SPARSE_BWD, PHMM_STATS_HINTED_WIDE = range(5)
 PHMM_READ_DEFERRED, PHMM_READ_WIDE_FRONTIER, PHMM_READ_FORCED_SWITCH = 1, 2, 4  # phmm_reads_last_call_info flags
 
 
@@ -129,3 +132,10 @@ DECLARED_SYMBOLS = [
 def check(rc: int) -> None:
     if rc != PHMM_OK:
         raise PhmmError(rc, lib().phmm_last_error().decode())
+
+
+def last_call_stats(which: int):
+    """(device ms, launches, cells) of kernel class `which` (PHMM_STATS_*) in this thread's most recent call."""
+    ms, n, c = C.c_double(), C.c_uint64(), C.c_uint64()
+    check(lib().phmm_last_call_stats(which, C.byref(ms), C.byref(n), C.byref(c)))
+    return ms.value, n.value, c.value

@@ -66,6 +66,10 @@ void refresh_knobs() {
     k.no_packed = flag("PHMM_NO_PACKED");
     k.packed_cpl = num("PHMM_PACKED_CPL", 0);
     k.no_exact_hinted = flag("PHMM_NO_EXACT_HINTED");
+    k.no_wide_hinted = flag("PHMM_NO_WIDE_HINTED");
+    k.wide_hinted = flag("PHMM_WIDE_HINTED") && !k.no_wide_hinted;
+    k.wide_hinted_cpb = num("PHMM_WIDE_HINTED_CPB", 0);
+    if (k.wide_hinted_cpb != 1 && k.wide_hinted_cpb != 2 && k.wide_hinted_cpb != 4) k.wide_hinted_cpb = 0;
     k.no_side_worker = flag("PHMM_NO_SIDE_WORKER");
     k.no_wide_handover = flag("PHMM_NO_WIDE_HANDOVER");
     k.workers = std::max(1, std::min(MAX_WORKERS, num("PHMM_WORKERS", 1)));
@@ -324,7 +328,7 @@ int phmm_enable_timing(int on) {
     return PHMM_OK;
 }
 int phmm_last_call_stats(int which, double *ms, uint64_t *launches, uint64_t *cells) {
-    if (which < 0 || which > 3) return fail(PHMM_EINVAL, "which out of range");
+    if (which < 0 || which > 4) return fail(PHMM_EINVAL, "which out of range");
     if (ms) *ms = g_stats.ms[which];
     if (launches) *launches = g_stats.launches[which];
     if (cells) *cells = g_stats.cells[which];

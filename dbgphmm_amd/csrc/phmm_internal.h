@@ -352,9 +352,9 @@ struct phmm_likelihood {
 namespace phmm {
 
 struct CallStats {
-    double ms[4] = {0, 0, 0, 0};
-    uint64_t launches[4] = {0, 0, 0, 0};
-    uint64_t cells[4] = {0, 0, 0, 0};
+    double ms[5] = {0, 0, 0, 0, 0};
+    uint64_t launches[5] = {0, 0, 0, 0, 0};
+    uint64_t cells[5] = {0, 0, 0, 0, 0};
 };
 CallStats &stats();
 bool timing_enabled();
@@ -401,6 +401,10 @@ struct Knobs {
     bool no_packed = false;          // PHMM_NO_PACKED: one candidate per wave
     int packed_cpl = 0;              // PHMM_PACKED_CPL: candidates per lane (0: automatic)
     bool no_exact_hinted = false;    // PHMM_NO_EXACT_HINTED: no wide-range pass over reads that a candidate cuts
+    bool wide_hinted = false;        // PHMM_WIDE_HINTED (and PHMM_NO_WIDE_HINTED unset): mapping lists of 65-400 nodes on a block
+                                     // (hinted_wide_kernel.h).  Opt-in until it is timed against the generic kernels
+    bool no_wide_hinted = false;     // PHMM_NO_WIDE_HINTED: generic kernels for mapping lists of 65-400 nodes (hinted forward)
+    int wide_hinted_cpb = 0;         // PHMM_WIDE_HINTED_CPB: candidates per block of that class, 1 / 2 / 4 (anything else, 0: automatic)
     bool no_side_worker = false;     // PHMM_NO_SIDE_WORKER
     bool no_wide_handover = false;   // PHMM_NO_WIDE_HANDOVER
     int workers = 1;                 // PHMM_WORKERS: chunk pipeline

@@ -612,6 +612,12 @@ __global__ void __launch_bounds__(64) hinted_packed_kernel(const HintedArgs a, c
     }
 }
 
+}  // namespace phmm
+
+#include "hinted_wide_kernel.h"
+
+namespace phmm {
+
 // ---- wide-range fallback of the hinted forward -----------------------------------------------------------
 // forward_with_mappings (forward.rs:79-89, 276-306, 337-388, 423-524, 541-558: fm, fi, fib, fd0 + n_max_gaps x fdt
 // over the position's list, fe at the end) with EVERY value carrying its own binary exponent -- a double mantissa
@@ -873,6 +879,60 @@ template <int CAP, int LPN> void launch_hinted(const HintedArgs &a, uint32_t n_r
     hipLaunchKernelGGL((hinted_score_kernel<CAP, LPN>), dim3(n_reads, n_cand), dim3(64), 0, current_stream(), a);
 }
 
+// hinted_wide_kernel: block class wc (0: lists of 65-128 nodes on 128 threads, 1: 129-400 on 448), cpb candidates per
+// block.  Which block shape or cpb ran a candidate does not show in its bits (hinted_wide_kernel.h).
+static constexpr uint32_t HW_MAX_LIST = 400;
+inline int hinted_wide_class(uint32_t mx) { return mx <= 128 ? 0 : 1; }
+// Candidates per block.  A guess, not a measurement: sharing a position's topology work among candidates is taken to
+// pay once the launch has 2 (4) times the pairs that 256 CUs hold as blocks of one candidate -- by registers 10 blocks
+// of 128 threads, 2 of 448 per CU (more candidates per block lower that to 6 / 4 resp. 2) --
+// and below that a block per pair keeps every read's chain of positions as short as it can be.
+inline int hinted_wide_cpb(int wc, uint64_t n_reads, uint64_t n_pairs) {
+    const uint64_t resident = wc == 0 ? 2560 : 512;
+    const uint64_t per_read = n_reads ? n_pairs / n_reads : 0;
+    int cpb = 1;
+    if (per_read >= 2 && n_pairs >= 2 * resident) cpb = 2;
+    if (per_read >= 4 && n_pairs >= 4 * resident) cpb = 4;
+    if (knobs().wide_hinted_cpb > 0) cpb = knobs().wide_hinted_cpb;  // (tests: every shape gives the same bits)
+    return wc == 0 ? (cpb >= 4 ? 4 : (cpb >= 2 ? 2 : 1)) : (cpb >= 2 ? 2 : 1);
+}
+template <bool PAIRS> void launch_hinted_wide(int wc, int cpb, const HintedArgs &a, dim3 grid, uint32_t n_cand) {
+    hipStream_t s = current_stream();
+    if (wc == 0) {
+        if (cpb >= 4) hipLaunchKernelGGL((hinted_wide_kernel<128, 4, PAIRS>), grid, dim3(128), 0, s, a, n_cand);
+        else if (cpb == 2) hipLaunchKernelGGL((hinted_wide_kernel<128, 2, PAIRS>), grid, dim3(128), 0, s, a, n_cand);
+        else hipLaunchKernelGGL((hinted_wide_kernel<128, 1, PAIRS>), grid, dim3(128), 0, s, a, n_cand);
+    } else {
+        if (cpb >= 2) hipLaunchKernelGGL((hinted_wide_kernel<448, 2, PAIRS>), grid, dim3(448), 0, s, a, n_cand);
+        else hipLaunchKernelGGL((hinted_wide_kernel<448, 1, PAIRS>), grid, dim3(448), 0, s, a, n_cand);
+    }
+}
+// The cells of a wide launch for the call statistics (list entries of the read x its candidates), added to *out on the
+// device: the position offsets of device-resident mappings are not on the host.  Units of `stride` words: {read} with
+// per_unit candidates each (stride 1), or {read, stride - 1 candidate slots} with 0xffffffff for an idle slot.
+__global__ void __launch_bounds__(256) hinted_wide_cells(const uint32_t *units, uint32_t n_units, uint32_t stride,
+                                                         uint32_t per_unit, const uint64_t *read_off,
+                                                         const uint64_t *map_pos_off, unsigned long long *out) {
+    const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long s = 0;
+    if (u < n_units) {
+        const uint32_t *w = units + (size_t)u * stride;
+        uint32_t k = per_unit;
+        if (stride > 1) {
+            k = 0;
+            for (uint32_t j = 1; j < stride; j++) k += w[j] != 0xffffffffu;
+        }
+        s = (unsigned long long)(map_pos_off[read_off[w[0] + 1]] - map_pos_off[read_off[w[0]]]) * k;
+    }
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
+}
+inline void launch_hinted_wide_cells(const HintedArgs &a, uint32_t n_units, uint32_t stride, uint32_t per_unit,
+                                     unsigned long long *d_cells) {
+    hipLaunchKernelGGL(hinted_wide_cells, dim3((n_units + 255) / 256), dim3(256), 0, current_stream(), a.read_ids, n_units,
+                       stride, per_unit, a.read_off, a.map_pos_off, d_cells);
+}
+
 }  // namespace
 
 // Candidate (init, trans) vectors straight from copy-number vectors, in the linear domain
@@ -970,17 +1030,23 @@ void full_prob_reads_hinted(phmm_model *m, const phmm_reads *reads, const phmm_m
 
     // capacity classes by the longest node list of each read.  Candidate batches: reads with short lists go to the
     // packed kernels (several candidates per wave) first.
-    std::vector<uint32_t> cls[3], pcls[3];
+    std::vector<uint32_t> cls[3], pcls[3], wcls[2];
     uint64_t cells = 0;
     const bool lean_ok = m->dev.max_degree <= (uint32_t)ADJ_DEG && !knobs().no_lean;
     const bool packed_ok = n_cand >= 2 && !pool && lean_ok && !knobs().no_packed;
+    // lists of 65-400 nodes: one block per read (hinted_wide_kernel.h).  By the read's lists, the model and the knobs
+    // only -- never by n_cand: a batch stays bit-equal to one-candidate calls.  The class is opt-in (PHMM_WIDE_HINTED):
+    // it has not been timed against the generic kernels, and speed is its only purpose
+    const bool wide_ok = lean_ok && !pool && knobs().wide_hinted;
     for (uint64_t r = 0; r < R; r++) {
         const uint32_t mx = mp->read_max_list[r];
         if (packed_ok && mx <= 32) pcls[mx <= 8 ? 0 : (mx <= 16 ? 1 : 2)].push_back((uint32_t)r);
+        else if (wide_ok && mx > 64 && mx <= HW_MAX_LIST) wcls[hinted_wide_class(mx)].push_back((uint32_t)r);
         else cls[mx <= 64 ? 0 : (mx <= 128 ? 1 : 2)].push_back((uint32_t)r);
     }
     DevBuf &d_ids = m->wset().aux[10], &d_out = m->wset().aux[11], &d_err = m->wset().aux[12];
-    d_ids.reserve(R * sizeof(uint32_t));
+    const size_t cells_at = (R * sizeof(uint32_t) + 7) / 8 * 8;  // (the cell counter of the wide class behind the ids)
+    d_ids.reserve(cells_at + sizeof(unsigned long long));
     d_out.reserve((size_t)n_cand * R * sizeof(double));
     d_err.reserve((size_t)n_cand * R * sizeof(uint32_t));
     std::vector<double> h_out((size_t)n_cand * R);
@@ -1032,6 +1098,33 @@ void full_prob_reads_hinted(phmm_model *m, const phmm_reads *reads, const phmm_m
             if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
             cls[0].push_back(rd);  // (cannot happen with read_max_list right: the one-candidate kernels take it)
         }
+    }
+    if (!wcls[0].empty() || !wcls[1].empty()) {
+        EvTimer tw(timing_enabled());
+        unsigned long long *d_cells = (unsigned long long *)(d_ids.as<char>() + cells_at), h_cells = 0;
+        HIP_CHECK(hipMemsetAsync(d_cells, 0, sizeof(unsigned long long), s));
+        for (int wc = 0; wc < 2; wc++) {
+            if (wcls[wc].empty()) continue;
+            HIP_CHECK(hipMemcpyAsync(d_ids.p, wcls[wc].data(), wcls[wc].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            const int cpb = hinted_wide_cpb(wc, wcls[wc].size(), (uint64_t)wcls[wc].size() * n_cand);
+            launch_hinted_wide<false>(wc, cpb, a, dim3((unsigned)wcls[wc].size(), (n_cand + cpb - 1) / cpb), n_cand);
+            launch_hinted_wide_cells(a, (uint32_t)wcls[wc].size(), 1, n_cand, d_cells);
+            HIP_CHECK(hipGetLastError());
+            st.launches[2]++;
+            st.launches[4]++;
+            HIP_CHECK(hipMemcpyAsync(h_err.data(), d_err.p, h_err.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(&h_cells, d_cells, sizeof(h_cells), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));  // (the read-id list is reused by the next class)
+            st.cells[4] = h_cells;  // (the counter runs over both classes)
+            for (uint32_t rd : wcls[wc]) {
+                uint32_t e = 0;
+                for (uint32_t k = 0; k < n_cand; k++) e |= h_err[(size_t)k * R + rd];
+                if (!e) continue;
+                if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
+                cls[mp->read_max_list[rd] <= 128 ? 1 : 2].push_back(rd);  // the generic kernel reports what it finds
+            }
+        }
+        st.ms[4] += tw.stop();
     }
     for (int c = 0; c < 3; c++) {
         if (cls[c].empty()) continue;
@@ -1437,11 +1530,13 @@ void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, 
         // capacity classes by the longest list of each read, as full_prob_reads_hinted has them
         const bool lean_ok = m->dev.max_degree <= (uint32_t)ADJ_DEG && !knobs().no_lean;
         const bool packed_ok = C >= 2 && lean_ok && !knobs().no_packed;
-        std::vector<uint32_t> cls[3], pcls[3];
+        const bool wide_ok = lean_ok && knobs().wide_hinted;
+        std::vector<uint32_t> cls[3], pcls[3], wcls[2];
         for (uint64_t r = 0; r < R; r++) {
             if (read_pair_off[r + 1] == read_pair_off[r]) continue;
             const uint32_t mx = mp->read_max_list[r];
             if (packed_ok && mx <= 32) pcls[mx <= 8 ? 0 : (mx <= 16 ? 1 : 2)].push_back((uint32_t)r);
+            else if (wide_ok && mx > 64 && mx <= HW_MAX_LIST) wcls[hinted_wide_class(mx)].push_back((uint32_t)r);
             else cls[mx <= 64 ? 0 : (mx <= 128 ? 1 : 2)].push_back((uint32_t)r);
         }
         // packed classes: work units {read, G x CPL slots}, the three classes behind one upload
@@ -1494,8 +1589,57 @@ void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, 
                 }
         }
         trace("cnc: packed classes");
+        // wide lists (65-400 nodes): work units {read, cpb slots}, only the touched pairs (hinted_wide_kernel.h)
+        if (!wcls[0].empty() || !wcls[1].empty()) {
+            EvTimer tw(timing_enabled());
+            std::vector<uint32_t> wu;
+            size_t wu_at[2], wu_n[2];
+            int wcpb[2];
+            for (int wc = 0; wc < 2; wc++) {
+                uint64_t np = 0;
+                for (uint32_t r : wcls[wc]) np += read_pair_off[r + 1] - read_pair_off[r];
+                wcpb[wc] = hinted_wide_cpb(wc, wcls[wc].size(), np);
+                wu_at[wc] = wu.size();
+                for (uint32_t r : wcls[wc])
+                    for (uint64_t q = read_pair_off[r]; q < read_pair_off[r + 1]; q += wcpb[wc]) {
+                        wu.push_back(r);
+                        for (int k = 0; k < wcpb[wc]; k++)
+                            wu.push_back(q + k < read_pair_off[r + 1] ? pairs[q + k].y : 0xffffffffu);
+                    }
+                wu_n[wc] = (wu.size() - wu_at[wc]) / (size_t)(1 + wcpb[wc]);
+            }
+            const size_t cells_at = (wu.size() * sizeof(uint32_t) + 7) / 8 * 8;  // (the cell counter behind the units)
+            d_ids.reserve(cells_at + sizeof(unsigned long long));
+            unsigned long long *d_cells = (unsigned long long *)(d_ids.as<char>() + cells_at), h_cells = 0;
+            HIP_CHECK(hipMemcpyAsync(d_ids.p, wu.data(), wu.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemsetAsync(d_cells, 0, sizeof(unsigned long long), s));
+            for (int wc = 0; wc < 2; wc++) {
+                if (!wu_n[wc]) continue;
+                HintedArgs au = a;
+                au.read_ids = d_ids.as<uint32_t>() + wu_at[wc];
+                launch_hinted_wide<true>(wc, wcpb[wc], au, dim3((unsigned)wu_n[wc]), D);
+                launch_hinted_wide_cells(au, (uint32_t)wu_n[wc], (uint32_t)(1 + wcpb[wc]), 0, d_cells);
+                HIP_CHECK(hipGetLastError());
+                stats().launches[2]++;
+                stats().launches[4]++;
+            }
+            HIP_CHECK(hipMemcpyAsync(&h_cells, d_cells, sizeof(h_cells), hipMemcpyDeviceToHost, s));
+            gather(false);
+            stats().cells[4] += h_cells;
+            for (int wc = 0; wc < 2; wc++)
+                for (uint32_t rd : wcls[wc]) {
+                    uint32_t e = 0;
+                    for (uint64_t q = read_pair_off[rd]; q < read_pair_off[rd + 1]; q++) e |= rerr[q];
+                    if (!e) continue;
+                    if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
+                    cls[mp->read_max_list[rd] <= 128 ? 1 : 2].push_back(rd);
+                }
+            stats().ms[4] += tw.stop();
+        }
+        trace("cnc: wide classes");
         // one-candidate classes; a read any of whose pairs overflows a class is promoted.  The lean class takes one
-        // {read, slot} pair per wave.  The generic kernels (lists over 64 nodes, or degree above ADJ_DEG; few reads) run
+        // {read, slot} pair per wave.  The generic kernels (what the lean and the wide class do not take: degree above ADJ_DEG,
+        // PHMM_NO_LEAN set, lists over 64 nodes while the wide class is not switched on, or a read one of them flagged) run
         // as in the full form, over the class's reads x the D candidates, and only the pairs are read back: a pair-list
         // instantiation of hinted_score_kernel would change the register allocation of the shared fwd_list_step in the
         // reads x candidates one, and a launch per candidate serialises long reads.

@@ -1048,7 +1048,7 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
         if (side_started && side_thread.joinable()) {
             side_thread.join();
             CallStats &st = stats();
-            for (int k = 0; k < 4; k++) {
+            for (int k = 0; k < 5; k++) {
                 st.ms[k] += side_stats.ms[k];
                 st.launches[k] += side_stats.launches[k];
                 st.cells[k] += side_stats.cells[k];
@@ -1077,7 +1077,7 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
                 (void)hipStreamSynchronize(m->pool->wstream[t]);
                 std::lock_guard<std::mutex> lk(mu);
                 const CallStats &ws = stats();
-                for (int k = 0; k < 4; k++) {
+                for (int k = 0; k < 5; k++) {
                     merged.ms[k] += ws.ms[k];
                     merged.launches[k] += ws.launches[k];
                     merged.cells[k] += ws.cells[k];

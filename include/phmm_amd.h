@@ -376,7 +376,12 @@ int phmm_run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const ph
  * Device time (ms, HIP events on the call's stream) and launch count of the dominant
  * kernel class in the most recent call of this thread, plus the algorithmic cell
  * count it processed (bench.py's roofline block).  which: 0 = dense forward step,
- * 1 = dense backward+posterior step, 2 = hinted/sparse forward, 3 = sparse backward. */
+ * 1 = dense backward+posterior step, 2 = hinted/sparse forward, 3 = sparse backward,
+ * 4 = the wide class of the hinted forward (reads whose longest mapping list holds
+ * 65-400 nodes, one block per read and candidate group; its launches and time are part
+ * of class 2 as well; cells = list entries x candidates it scored; all 0 when the call
+ * had no such read or the class is off: it is opt-in, PHMM_WIDE_HINTED=1, and
+ * PHMM_NO_WIDE_HINTED=1 wins over that).  Any other index is PHMM_EINVAL. */
 int phmm_last_call_stats(int which, double *out_ms, uint64_t *out_launches,
                          uint64_t *out_cells);
 int phmm_enable_timing(int on);
