@@ -79,6 +79,7 @@ void refresh_knobs() {
     k.pipeline_min_groups = std::max(1, num("PHMM_PIPELINE_MIN_GROUPS", 8));
     k.no_runmax = flag("PHMM_NO_RUNMAX");
     k.force_radix = flag("PHMM_FORCE_RADIX");
+    k.no_bwd_skip = flag("PHMM_NO_BWD_SKIP");
     k.serial_emit = flag("PHMM_SERIAL_EMIT");
     k.emit_high_priority = flag("PHMM_EMIT_HIGH_PRIORITY");
     k.no_dma = flag("PHMM_NO_DMA");

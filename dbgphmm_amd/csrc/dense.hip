@@ -559,7 +559,36 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
     // A block none of whose lanes has this column (a read group past its last dense backward column: groups are
     // sorted by their reads' switch positions, so whole groups go quiet at the high columns) leaves its zero partial
     // sums and is done; without this it walked its run of rows for nothing.
-    if (!__syncthreads_or(live)) {
+    // Run skipping (masks given, W == 64: a row is a wave and its lanes are the reads of the group).  B of column pos
+    // can be non-zero in a run only if a read whose dense columns have begun was handed a non-zero value in it (H:
+    // one bit per hand-over column s0 + 1, this launch looks at the bits above pos), if the column before was computed
+    // in it or in a run its nodes reach (A of the other parity), or if a read starts here (`first`: b_init is p_end
+    // at every node).  A run that was never computed holds +0.0 in both B buffers and both emit-prob planes for
+    // every live lane (the host cleared them; a hand-over of a read that is not live yet is the one thing it may
+    // hold), a run computed once is computed in every later column: nothing stale, and a row that does not compute
+    // contributes exactly the zeros it would have computed.  Each row writes only its own byte of this column's
+    // parity and reads only the other parity.
+    bool compute = true;
+    if (W == 64 && a.skA) {
+        compute = false;
+        const int rho = __builtin_amdgcn_readfirstlane(lb * ROWS + row);
+        if (__any(live) && rho < a.nrun) {
+            const size_t gr = (size_t)g * a.nrun, par = (size_t)a.ng * a.nrun;
+            const uint32_t *hh = a.skH + gr;
+            const uint8_t *an = a.skA + (size_t)((pos + 1) & 1) * par + gr;
+            const int sh = pos + 1 < 31 ? pos + 1 : 31;
+            unsigned f = (hh[rho] >> sh) | (unsigned)an[rho] | (__any(first) ? 1u : 0u);
+            const uint32_t o0 = a.rs_off[rho], o1 = a.rs_off[rho + 1];
+            for (uint32_t q = o0; q < o1 && !f; q++) {
+                const uint32_t t = a.rs[q];
+                f = (hh[t] >> sh) | (unsigned)an[t];
+            }
+            compute = __builtin_amdgcn_readfirstlane((int)f) != 0;
+            if ((threadIdx.x & 63) == 0) a.skA[(size_t)(pos & 1) * par + gr + rho] = compute ? 1 : 0;
+        }
+    }
+    // (block 0 of a live group goes on in any case: it writes BE[pos])
+    if (!__syncthreads_or(live && (compute || lb == 0))) {
         if (threadIdx.x < W && lb < a.nblk) {
             double *bp = a.bpart + ((size_t)(pos & 1) * a.ng + g) * a.nblk8 * W * 2;
             bp[((size_t)lb * W + r) * 2 + 0] = 0.0;
@@ -613,7 +642,7 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
     double vmax = 0.0, s1 = 0.0, s2 = 0.0, pmx = 0.0, pmx2 = 0.0;
     double *Pa = a.want_map ? a.Pa + (size_t)g * NW : nullptr;
     double *Pb = a.want_map ? a.Pb + (size_t)g * NW : nullptr;
-    if (lb < a.nblk) {
+    if (lb < a.nblk && compute) {
         // Rows walk their run of npt consecutive nodes in DECREASING order; on a unitig run
         // (CHAIN_B: the descendants within 6 hops are v+1 .. v+6 with unit weights) the values
         // h[u] = e_u(x) m'[u], q[u] = p_r i'[u] come from a register window fed by own loads.
@@ -647,6 +676,10 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
                  : 0u;
         const double *ring_w = &ring[DMA_ ? (threadIdx.x >> 6) * BDMA_DEPTH * BDMA_SLOT : 0];
         const int n1 = __any(live) ? 2 + (od ? 1 : 0) : 0;
+        if (W == 64 && a.skcells) {
+            const unsigned long long nlive = (unsigned long long)__popcll(__ballot(live));
+            if (l64 == 0 && jtop >= 0) atomicAdd(a.skcells, nlive * (unsigned long long)(jtop + 1));
+        }
         const int ns = n1 + ((a.want_map && __any(live)) ? 1 : 0) + (a.want_freq ? 2 : 0);
 #pragma unroll
         for (int u = 0; u < PFB; u++) {

@@ -448,6 +448,8 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
             for (int j = lane; j < c.n; j += 64) {
                 bm[(size_t)c.id[j] * a.W + r] = c.m[j];
                 bi[(size_t)c.id[j] * a.W + r] = c.i[j];
+                if (a.d.skH && (c.m[j] != 0.0 || c.i[j] != 0.0))  // (run skipping, dense.hip: the run counts from column s0 on)
+                    atomicOr(&a.d.skH[(size_t)g * a.d.nrun + c.id[j] / (uint32_t)a.d.npt], 1u << (s0 + 1 < 31 ? s0 + 1 : 31));
                 mx = fmax(mx, fmax(c.m[j], c.i[j]));
             }
             mx = wave_max(mx);
@@ -1004,6 +1006,10 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
         pos_max = std::max(pos_max, hb[gi] & ~(1 << 30));
     }
     DevBuf &ctl = m->wset().aux[3], &pbuf = m->wset().aux[4];
+    // bwd_step<64> walks only the node runs in which B can be non-zero (PHMM_NO_BWD_SKIP=1: every run, as the other
+    // widths do)
+    const bool skip = W == 64 && !knobs().no_bwd_skip && pos_max >= 0;
+    const RunSucc *rsucc = skip ? &model_run_successors(m, mc.a.npt) : nullptr;
     size_t cb = 0;
     auto carve = [&](size_t bytes) {
         cb = (cb + 255) / 256 * 256;
@@ -1012,9 +1018,11 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
         return o;
     };
     const size_t o_bs = carve(sizeof(int) * lanes), o_ca = carve(sizeof(int) * lanes * 2), o_cb = carve(sizeof(int) * lanes * 2),
-                 o_err = carve(sizeof(uint32_t) * lanes), o_lanes = carve(sizeof(uint32_t) * std::max<size_t>(sparse_lanes.size(), 1)),
+                 o_err = carve(sizeof(uint32_t) * lanes), o_cells = carve(sizeof(unsigned long long)), o_lanes = carve(sizeof(uint32_t) * std::max<size_t>(sparse_lanes.size(), 1)),
                  o_lp0 = carve(sizeof(uint64_t) * (lanes + 1)), o_gp0 = carve(sizeof(uint64_t) * (lanes + 1)),
                  o_stop = carve(sizeof(int) * lanes),
+                 // run masks of bwd_step<64> (dense.hip): H [ngc][nrun], A [2][ngc][nrun]
+                 o_skh = carve(skip ? sizeof(uint32_t) * (size_t)mc.a.ng * rsucc->nrun : 0), o_ska = carve(skip ? 2 * (size_t)mc.a.ng * rsucc->nrun : 0),
                  o_bn = carve(sizeof(uint32_t) * (size_t)lanes * KMAX * 2), o_bv = carve(sizeof(double) * (size_t)lanes * KMAX * 2),
                  o_an = carve(sizeof(uint32_t) * (size_t)lanes * KMAX * 2), o_av = carve(sizeof(double) * (size_t)lanes * KMAX * 2),
                  o_hand = carve(sizeof(BHandoff) * (size_t)lanes), o_eoff = carve(sizeof(unsigned long long) * 2 * (size_t)lanes),
@@ -1049,6 +1057,21 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
         a.Pa = pbuf.as<double>();
         a.Pb = need_pb ? pbuf.as<double>() + 2 * (size_t)mc.ngc * NW : pbuf.as<double>();  // (never touched without such a read)
         a.Prun = knobs().no_runmax ? nullptr : pbuf.as<double>() + (need_pb ? 3 : 2) * (size_t)mc.ngc * NW;
+        const bool st_on = W == 64 && mc.main_plan;  // statistics of the main plan's bwd_step<64> only (bench.py's roofline)
+        if (skip) {
+            // (the masks and the counter were cleared with the control block above)
+            a.rs_off = rsucc->off.as<uint32_t>();
+            a.rs = rsucc->ent.as<uint32_t>();
+            a.nrun = (int)rsucc->nrun;
+            a.skH = (uint32_t *)(cp + o_skh);
+            a.skA = (uint8_t *)(cp + o_ska);
+            a.skcells = st_on ? (unsigned long long *)(cp + o_cells) : nullptr;
+            // a run that is never computed keeps what the planes held: the column selects of emit_dense_map and a
+            // post_collect without run maxima read whole columns of them.  These are the two Pa parities; Pb (the plane
+            // of merged index `len`) needs no clearing: only a `first` lane writes and reads it, and a `first` lane makes
+            // every row of its group compute in that launch, so its whole column of Pb is written there.
+            HIP_CHECK(hipMemsetAsync(pbuf.p, 0, sizeof(double) * 2 * (size_t)mc.ngc * NW, s));
+        }
         // backward scratch of the chunk must start clean (a previous attempt may have used it)
         HIP_CHECK(hipMemsetAsync(a.cmaxB, 0, sizeof(unsigned long long) * (size_t)a.ng * a.Lc * W, s));
         HIP_CHECK(hipMemsetAsync(a.pmax, 0, sizeof(unsigned long long) * (size_t)a.ng * (a.Lc + 1) * W, s));
@@ -1171,7 +1194,6 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
             if (hb[gi] >= 0) live_at[(size_t)(hb[gi] & ~(1 << 30))]++;
         for (int p = pos_max - 1; p >= 0; p--) live_at[(size_t)p] += live_at[(size_t)p + 1];
         ma.force_radix = knobs().force_radix ? 1 : 0;
-        const bool st_on = W == 64 && mc.main_plan;  // statistics of the main plan's bwd_step<64> only (bench.py's roofline)
         LaunchTimer lt(timing_enabled() && st_on);
         std::unique_lock<std::mutex> dense_lock;
         if (mc.dense_token) dense_lock = std::unique_lock<std::mutex>(*mc.dense_token);
@@ -1237,11 +1259,18 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
         }
         st.ms[1] += lt.total_ms();
         for (int gi = 0; gi < lanes; gi++)
-            if (st_on && hb[gi] >= 0) st.cells[1] += (uint64_t)((hb[gi] & ~(1 << 30)) + 1) * m->N;
-        std::vector<uint32_t> herr(lanes);
-        HIP_CHECK(hipMemcpyAsync(herr.data(), cp + o_err, sizeof(uint32_t) * lanes, hipMemcpyDeviceToHost, s));
+            if (st_on && !a.skcells && hb[gi] >= 0) st.cells[1] += (uint64_t)((hb[gi] & ~(1 << 30)) + 1) * m->N;
+        // the error words and, behind them, the cells of the runs bwd_step computed: one copy
+        const size_t err_words = (o_cells + sizeof(unsigned long long) - o_err) / sizeof(uint32_t);
+        std::vector<uint32_t> herr(err_words);
+        HIP_CHECK(hipMemcpyAsync(herr.data(), cp + o_err, sizeof(uint32_t) * err_words, hipMemcpyDeviceToHost, s));
         if (want_lb) HIP_CHECK(hipMemcpyAsync(mc.logb_out, cp + o_lb, sizeof(double) * lanes, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
+        if (a.skcells) {
+            unsigned long long nc = 0;
+            memcpy(&nc, herr.data() + (o_cells - o_err) / sizeof(uint32_t), sizeof nc);
+            st.cells[1] += nc;
+        }
         if (dense_lock.owns_lock()) dense_lock.unlock();
         trace("  dense backward+collect");
         bool pool_full = false;

@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "phmm_internal.h"
+#include "run_succ.h"
 
 namespace phmm {
 
@@ -206,6 +207,16 @@ void model_upload(phmm_model *m) {
         bc_off[k + 1] = (uint32_t)bc.size();
     }
 
+    // the descendants within the closure's hops, for the run successors (run_succ.h); the weights may have changed
+    // which edges count, so the lists built from the previous closure go
+    m->desc_off = bh_off;
+    m->desc_node.resize(bh.size());
+    for (size_t q = 0; q < bh.size(); q++) m->desc_node[q] = bh[q].node;
+    {
+        std::lock_guard<std::mutex> lk(m->rs_mu);
+        m->rs_cache.clear();
+    }
+
     ModelDev &d = m->dev;
     d.N = N;
     d.E = E;
@@ -290,6 +301,23 @@ void model_upload(phmm_model *m) {
     d.logib_len = 0;  // parameters may have changed
     // the host vectors above die at scope exit: make sure the async copies are done
     HIP_CHECK(hipStreamSynchronize(current_stream()));
+}
+
+const RunSucc &model_run_successors(phmm_model *m, int npt) {
+    std::lock_guard<std::mutex> lk(m->rs_mu);
+    for (const auto &e : m->rs_cache)
+        if (e->npt == npt) return *e;
+    std::vector<uint32_t> off, ent;
+    build_run_successors(m->N, (uint32_t)npt, m->desc_off, m->desc_node, off, ent);
+    std::unique_ptr<RunSucc> e(new RunSucc);
+    e->npt = npt;
+    e->nrun = (uint32_t)off.size() - 1;
+    e->off.upload(off.data(), sizeof(uint32_t) * off.size());
+    e->ent.upload(ent.data(), sizeof(uint32_t) * ent.size());
+    e->ent.reserve(sizeof(uint32_t));  // (no successor anywhere: still a pointer)
+    HIP_CHECK(hipStreamSynchronize(current_stream()));
+    m->rs_cache.push_back(std::move(e));
+    return *m->rs_cache.back();
 }
 
 // forward InsBegin chain in the log domain: ib_0 = p_r*(p_MI*1 + p_II*0); ib_i = p_r*p_II*ib_{i-1}

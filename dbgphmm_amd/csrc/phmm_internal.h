@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -256,6 +257,13 @@ struct ModelDev {
     uint32_t max_degree = 0;
 };
 
+// Run successors for one run length (run_succ.h), on the device: what bwd_step's run skipping reads
+struct RunSucc {
+    int npt = 0;
+    uint32_t nrun = 0;
+    DevBuf off, ent;  // u32[nrun+1], u32[]
+};
+
 }  // namespace phmm
 
 struct phmm_model {
@@ -270,6 +278,11 @@ struct phmm_model {
     std::vector<double> logib;  // forward InsBegin chain, log domain (forward.rs:541-545)
     phmm::ModelDev dev;
     double wf_ub_a = 0.0, wf_ub_b = 0.0;  // column total <= ub_a * max(m,i) + ub_b * p_ID * ib (model.cpp)
+    // nodes of the descendant hop entries (bh) per node, kept on the host for the run successors, and the run
+    // successors built so far, by run length (the plans of one model use few); model_upload drops them
+    std::vector<uint32_t> desc_off, desc_node;
+    std::mutex rs_mu;
+    std::vector<std::unique_ptr<phmm::RunSucc>> rs_cache;
     // Workspaces (DP tables, record pools, per-call scratch) belong to the DEVICE, not to the model: every
     // handle on a device shares one phmm::DevicePool, so a mapping model and a scoring model coexist
     // (multi_dbg/posterior.rs:247-255, 609-630) without each sizing its own tables from what is free.
@@ -418,6 +431,7 @@ struct Knobs {
     bool emit_high_priority = false; // PHMM_EMIT_HIGH_PRIORITY: list kernels of the dense head at the highest stream priority
     bool no_dma = false;             // PHMM_NO_DMA: forward rows through registers
     bool bwd_dma = false;            // PHMM_BWD_DMA
+    bool no_bwd_skip = false;        // PHMM_NO_BWD_SKIP: the dense head's bwd_step computes every node run (no run masks)
     int dense_streams = 0;           // PHMM_DENSE_STREAMS
     int dense_w = 0;                 // PHMM_DENSE_W
     int dense_npt = 0;               // PHMM_DENSE_NPT
@@ -428,6 +442,7 @@ void refresh_knobs();
 
 void model_build_host(phmm_model *m);    // CSR + logib
 void model_upload(phmm_model *m);        // closures + device arrays
+const RunSucc &model_run_successors(phmm_model *m, int npt);  // built and uploaded on first use of a run length
 
 // dense driver (dense.hip)
 void run_dense(phmm_model *m, const phmm_reads *reads, double *out_lf, double *out_lb,
