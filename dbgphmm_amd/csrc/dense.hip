@@ -559,32 +559,48 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
     // A block none of whose lanes has this column (a read group past its last dense backward column: groups are
     // sorted by their reads' switch positions, so whole groups go quiet at the high columns) leaves its zero partial
     // sums and is done; without this it walked its run of rows for nothing.
-    // Run skipping (masks given, W == 64: a row is a wave and its lanes are the reads of the group).  B of column pos
-    // can be non-zero in a run only if a read whose dense columns have begun was handed a non-zero value in it (H:
-    // one bit per hand-over column s0 + 1, this launch looks at the bits above pos), if the column before was computed
-    // in it or in a run its nodes reach (A of the other parity), or if a read starts here (`first`: b_init is p_end
-    // at every node).  A run that was never computed holds +0.0 in both B buffers and both emit-prob planes for
-    // every live lane (the host cleared them; a hand-over of a read that is not live yet is the one thing it may
-    // hold), a run computed once is computed in every later column: nothing stale, and a row that does not compute
-    // contributes exactly the zeros it would have computed.  Each row writes only its own byte of this column's
-    // parity and reads only the other parity.
+    // Run skipping (masks given, W == 64: a row is a wave and its lanes are the reads of the group).  The masks are kept
+    // per SEGMENT of sseg nodes, 8 to a run (one when npt is no multiple of 8: seg_hull.h).  B of column pos can be
+    // non-zero in a segment only if a read whose dense columns have begun was handed a non-zero value in it (H: one bit
+    // per hand-over column s0 + 1, this launch looks at the bits above pos), if the column before was marked in it or
+    // in a segment its nodes reach (A of the other parity, one bit per segment in the run's byte), or if a read starts
+    // here (`first`: b_init is p_end at every node).  Lanes 0..7 of the row evaluate one segment each, a ballot makes
+    // the run's mask, and the row walks the HULL of its marked segments: the first node walked rebuilds its window
+    // from the hop entries as the first node of a run does, which gives the bits the sliding window would have held
+    // (the same Horner nest over the same per-hop sums).  A records the marks, not the hull.
+    // A segment that was never marked holds +0.0 in both B buffers and both emit-prob planes for every live lane (the
+    // host cleared them; a hand-over of a read that is not live yet is the one thing it may hold), a segment marked
+    // once is marked in every later column (the self term), and a cell inside the hull but outside the marks has
+    // itself and all its hop descendants unmarked one column later, so it stores the +0.0 it computes over +0.0:
+    // nothing stale, and what is not walked contributes exactly the zeros it would have computed.  Each row writes
+    // only its own byte of this column's parity and reads only the other parity.
     bool compute = true;
+    int hull_first = 0, hull_top = a.npt - 1;
     if (W == 64 && a.skA) {
         compute = false;
         const int rho = __builtin_amdgcn_readfirstlane(lb * ROWS + row);
         if (__any(live) && rho < a.nrun) {
-            const size_t gr = (size_t)g * a.nrun, par = (size_t)a.ng * a.nrun;
-            const uint32_t *hh = a.skH + gr;
+            const size_t gs = (size_t)g * a.nseg, gr = (size_t)g * a.nrun, par = (size_t)a.ng * a.nrun;
+            const uint32_t *hh = a.skH + gs;
             const uint8_t *an = a.skA + (size_t)((pos + 1) & 1) * par + gr;
             const int sh = pos + 1 < 31 ? pos + 1 : 31;
-            unsigned f = (hh[rho] >> sh) | (unsigned)an[rho] | (__any(first) ? 1u : 0u);
-            const uint32_t o0 = a.rs_off[rho], o1 = a.rs_off[rho + 1];
-            for (uint32_t q = o0; q < o1 && !f; q++) {
-                const uint32_t t = a.rs[q];
-                f = (hh[t] >> sh) | (unsigned)an[t];
+            const int sprs = segs_per_run_log2(a.npt), spr = 1 << sprs;  // segments per run (8 or 1) and its log2
+            const unsigned anyfirst = __any(first) ? 1u : 0u;
+            const int ls = threadIdx.x & 63;
+            const int sg = rho * spr + ls;
+            unsigned f = 0;
+            if (ls < spr && sg < a.nseg) {
+                f = (hh[sg] >> sh) | (((unsigned)an[rho] >> ls) & 1u) | anyfirst;
+                const uint32_t o0 = a.rs_off[sg], o1 = a.rs_off[sg + 1];
+                for (uint32_t q = o0; q < o1 && !f; q++) {
+                    const uint32_t t = a.rs[q];
+                    f = (hh[t] >> sh) | (((unsigned)an[t >> sprs] >> (t & (uint32_t)(spr - 1))) & 1u);
+                }
             }
-            compute = __builtin_amdgcn_readfirstlane((int)f) != 0;
-            if ((threadIdx.x & 63) == 0) a.skA[(size_t)(pos & 1) * par + gr + rho] = compute ? 1 : 0;
+            const unsigned mask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__ballot(f != 0));
+            const int kb = rho * a.npt;
+            compute = seg_hull(mask, a.sseg, a.npt - 1 < a.N - 1 - kb ? a.npt - 1 : a.N - 1 - kb, &hull_first, &hull_top);
+            if (ls == 0) a.skA[(size_t)(pos & 1) * par + gr + rho] = (uint8_t)mask;
         }
     }
     // (block 0 of a live group goes on in any case: it writes BE[pos])
@@ -647,7 +663,8 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
         // (CHAIN_B: the descendants within 6 hops are v+1 .. v+6 with unit weights) the values
         // h[u] = e_u(x) m'[u], q[u] = p_r i'[u] come from a register window fed by own loads.
         constexpr int H = CHAIN_HOPS;
-        const int kbase = lb * (a.npt * ROWS) + row * a.npt;
+        // (run skipping: from the first node of the row's hull on)
+        const int kbase = lb * (a.npt * ROWS) + row * a.npt + hull_first;
         // partial sums over the per-hop sums of h, q at the descendants (column pos+1, rescaled): E_j = sum_{h < j}
         // p_DD^h Hs[h], Q_j likewise, TE = the E_{G+1} of the node above
         double E1 = 0.0, E2 = 0.0, E3 = 0.0, E4 = 0.0, E5 = 0.0, Q1 = 0.0, Q2 = 0.0, Q3 = 0.0, Q4 = 0.0, Q5 = 0.0, TE = 0.0;
@@ -660,8 +677,8 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
         constexpr int PFB = DMA_ ? BDMA_DEPTH : PHMM_BWD_PF;
         double nx_m[PFB], nx_i[PFB], nx_fm[PFB], nx_fi[PFB], nx_fd[PFB];
         const double *lfm = want_post ? fm : nm, *lfi = want_post ? fi : nm, *lfd = want_post ? fd : nm;
-        // rows kbase+jtop .. kbase (jtop clamps the last block of the column)
-        const int jtop = a.npt - 1 < a.N - 1 - kbase ? a.npt - 1 : a.N - 1 - kbase;
+        // rows kbase+jtop .. kbase (jtop clamps the last block of the column, and ends at the top of the row's hull)
+        const int jtop = hull_top < a.N - 1 - kbase ? hull_top : a.N - 1 - kbase;
         // LDS-DMA variant (see fwd_step): three requests per row -- A: B' m | B' i, B: F m | F i, C: F d (lower
         // half of the wave) -- into slot u of this wave's ring; A is consumed at the top of a row and requested
         // again there, B and C at its end.  Vector-memory operations of a row besides the 3 requests: n1 stores

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "phmm_internal.h"
+#include "seg_hull.h"
 
 namespace phmm {
 
@@ -70,13 +71,14 @@ struct DenseArgs {
     double wf_ratio;               // exp(-active_node_max_ratio)
     double wf_ub_a, wf_ub_b;       // column total <= wf_ub_a * max(m,i) + wf_ub_b * p_ID * ib   (model.cpp)
     // Run skipping of bwd_step<64> (mapping flow, DESIGN.md section 6, "Run skipping"); skA null: every run is computed.
-    // A run is the npt nodes of one row, rho = node / npt.
-    const uint32_t *rs_off = nullptr, *rs = nullptr;  // [nrun+1], []: the other runs a run's nodes reach (run_succ.h)
-    uint32_t *skH = nullptr;       // [ng][nrun] bit min(s0 + 1, 31): a read of the group whose last dense column is s0 was
-                                   // handed a non-zero value at a node of the run (set by the hand-over kernels)
-    uint8_t *skA = nullptr;        // [2][ng][nrun] by column parity: the run was computed in that column
-    int nrun = 0;
-    unsigned long long *skcells = nullptr;  // live lanes x rows of the runs computed (null: not counted)
+    // A run is the npt nodes of one row, rho = node / npt; a segment is sseg nodes, sigma = node / sseg, and a run
+    // holds npt / sseg of them: 8, or 1 when npt is no multiple of 8 (seg_hull.h).
+    const uint32_t *rs_off = nullptr, *rs = nullptr;  // [nseg+1], []: the other segments a segment's nodes reach (run_succ.h)
+    uint32_t *skH = nullptr;       // [ng][nseg] bit min(s0 + 1, 31): a read of the group whose last dense column is s0 was
+                                   // handed a non-zero value at a node of the segment (set by the hand-over kernels)
+    uint8_t *skA = nullptr;        // [2][ng][nrun] by column parity: bit s = segment s of the run was marked in that column
+    int nrun = 0, nseg = 0, sseg = 1;
+    unsigned long long *skcells = nullptr;  // live lanes x rows walked (the hulls of the marked segments; null: not counted)
 };
 static constexpr int WF_CAP = 1024;
 

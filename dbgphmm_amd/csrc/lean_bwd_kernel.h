@@ -572,8 +572,8 @@ __global__ void __launch_bounds__(64, 4) lean_backward_kernel(const SparseBwdArg
             if (inprev) {
                 bmp[(size_t)id * a.W + r] = pm;
                 bip[(size_t)id * a.W + r] = pi;
-                if (a.d.skH && (pm != 0.0 || pi != 0.0))  // (run skipping, dense.hip: the run counts from column s0 on)
-                    atomicOr(&a.d.skH[(size_t)g * a.d.nrun + id / (uint32_t)a.d.npt], 1u << (s0 + 1 < 31 ? s0 + 1 : 31));
+                if (a.d.skH && (pm != 0.0 || pi != 0.0))  // (run skipping, dense.hip: the segment counts from column s0 on)
+                    atomicOr(&a.d.skH[(size_t)g * a.d.nseg + id / (uint32_t)a.d.sseg], 1u << (s0 + 1 < 31 ? s0 + 1 : 31));
                 mx = fmax(pm, pi);
             }
             mx = wave_max(mx);

@@ -448,8 +448,8 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
             for (int j = lane; j < c.n; j += 64) {
                 bm[(size_t)c.id[j] * a.W + r] = c.m[j];
                 bi[(size_t)c.id[j] * a.W + r] = c.i[j];
-                if (a.d.skH && (c.m[j] != 0.0 || c.i[j] != 0.0))  // (run skipping, dense.hip: the run counts from column s0 on)
-                    atomicOr(&a.d.skH[(size_t)g * a.d.nrun + c.id[j] / (uint32_t)a.d.npt], 1u << (s0 + 1 < 31 ? s0 + 1 : 31));
+                if (a.d.skH && (c.m[j] != 0.0 || c.i[j] != 0.0))  // (run skipping, dense.hip: the segment counts from column s0 on)
+                    atomicOr(&a.d.skH[(size_t)g * a.d.nseg + c.id[j] / (uint32_t)a.d.sseg], 1u << (s0 + 1 < 31 ? s0 + 1 : 31));
                 mx = fmax(mx, fmax(c.m[j], c.i[j]));
             }
             mx = wave_max(mx);
@@ -1006,10 +1006,12 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
         pos_max = std::max(pos_max, hb[gi] & ~(1 << 30));
     }
     DevBuf &ctl = m->wset().aux[3], &pbuf = m->wset().aux[4];
-    // bwd_step<64> walks only the node runs in which B can be non-zero (PHMM_NO_BWD_SKIP=1: every run, as the other
-    // widths do)
+    // bwd_step<64> walks only the part of each node run in which B can be non-zero, by masks per segment of a run
+    // (PHMM_NO_BWD_SKIP=1: every run in full, as the other widths do)
     const bool skip = W == 64 && !knobs().no_bwd_skip && pos_max >= 0;
-    const RunSucc *rsucc = skip ? &model_run_successors(m, mc.a.npt) : nullptr;
+    const int sseg = seg_size(mc.a.npt);
+    const RunSucc *rsucc = skip ? &model_run_successors(m, sseg) : nullptr;
+    const size_t sk_nrun = ((size_t)m->N + mc.a.npt - 1) / mc.a.npt;
     size_t cb = 0;
     auto carve = [&](size_t bytes) {
         cb = (cb + 255) / 256 * 256;
@@ -1021,8 +1023,8 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
                  o_err = carve(sizeof(uint32_t) * lanes), o_cells = carve(sizeof(unsigned long long)), o_lanes = carve(sizeof(uint32_t) * std::max<size_t>(sparse_lanes.size(), 1)),
                  o_lp0 = carve(sizeof(uint64_t) * (lanes + 1)), o_gp0 = carve(sizeof(uint64_t) * (lanes + 1)),
                  o_stop = carve(sizeof(int) * lanes),
-                 // run masks of bwd_step<64> (dense.hip): H [ngc][nrun], A [2][ngc][nrun]
-                 o_skh = carve(skip ? sizeof(uint32_t) * (size_t)mc.a.ng * rsucc->nrun : 0), o_ska = carve(skip ? 2 * (size_t)mc.a.ng * rsucc->nrun : 0),
+                 // segment masks of bwd_step<64> (dense.hip): H [ngc][nseg], A [2][ngc][nrun]
+                 o_skh = carve(skip ? sizeof(uint32_t) * (size_t)mc.a.ng * rsucc->nseg : 0), o_ska = carve(skip ? 2 * (size_t)mc.a.ng * sk_nrun : 0),
                  o_bn = carve(sizeof(uint32_t) * (size_t)lanes * KMAX * 2), o_bv = carve(sizeof(double) * (size_t)lanes * KMAX * 2),
                  o_an = carve(sizeof(uint32_t) * (size_t)lanes * KMAX * 2), o_av = carve(sizeof(double) * (size_t)lanes * KMAX * 2),
                  o_hand = carve(sizeof(BHandoff) * (size_t)lanes), o_eoff = carve(sizeof(unsigned long long) * 2 * (size_t)lanes),
@@ -1062,11 +1064,13 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
             // (the masks and the counter were cleared with the control block above)
             a.rs_off = rsucc->off.as<uint32_t>();
             a.rs = rsucc->ent.as<uint32_t>();
-            a.nrun = (int)rsucc->nrun;
+            a.nseg = (int)rsucc->nseg;
+            a.sseg = sseg;
+            a.nrun = (int)sk_nrun;
             a.skH = (uint32_t *)(cp + o_skh);
             a.skA = (uint8_t *)(cp + o_ska);
             a.skcells = st_on ? (unsigned long long *)(cp + o_cells) : nullptr;
-            // a run that is never computed keeps what the planes held: the column selects of emit_dense_map and a
+            // a segment that is never walked keeps what the planes held: the column selects of emit_dense_map and a
             // post_collect without run maxima read whole columns of them.  These are the two Pa parities; Pb (the plane
             // of merged index `len`) needs no clearing: only a `first` lane writes and reads it, and a `first` lane makes
             // every row of its group compute in that launch, so its whole column of Pb is written there.

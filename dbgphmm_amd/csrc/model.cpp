@@ -303,15 +303,15 @@ void model_upload(phmm_model *m) {
     HIP_CHECK(hipStreamSynchronize(current_stream()));
 }
 
-const RunSucc &model_run_successors(phmm_model *m, int npt) {
+const RunSucc &model_run_successors(phmm_model *m, int seg) {
     std::lock_guard<std::mutex> lk(m->rs_mu);
     for (const auto &e : m->rs_cache)
-        if (e->npt == npt) return *e;
+        if (e->seg == seg) return *e;
     std::vector<uint32_t> off, ent;
-    build_run_successors(m->N, (uint32_t)npt, m->desc_off, m->desc_node, off, ent);
+    build_run_successors(m->N, (uint32_t)seg, m->desc_off, m->desc_node, off, ent);
     std::unique_ptr<RunSucc> e(new RunSucc);
-    e->npt = npt;
-    e->nrun = (uint32_t)off.size() - 1;
+    e->seg = seg;
+    e->nseg = (uint32_t)off.size() - 1;
     e->off.upload(off.data(), sizeof(uint32_t) * off.size());
     e->ent.upload(ent.data(), sizeof(uint32_t) * ent.size());
     e->ent.reserve(sizeof(uint32_t));  // (no successor anywhere: still a pointer)

@@ -257,11 +257,12 @@ struct ModelDev {
     uint32_t max_degree = 0;
 };
 
-// Run successors for one run length (run_succ.h), on the device: what bwd_step's run skipping reads
+// Successors for one segment length (run_succ.h with the segment as its run; seg_hull.h), on the device: what
+// bwd_step's run skipping reads
 struct RunSucc {
-    int npt = 0;
-    uint32_t nrun = 0;
-    DevBuf off, ent;  // u32[nrun+1], u32[]
+    int seg = 0;        // nodes per segment
+    uint32_t nseg = 0;  // segments
+    DevBuf off, ent;  // u32[nseg+1], u32[]
 };
 
 }  // namespace phmm
@@ -278,8 +279,8 @@ struct phmm_model {
     std::vector<double> logib;  // forward InsBegin chain, log domain (forward.rs:541-545)
     phmm::ModelDev dev;
     double wf_ub_a = 0.0, wf_ub_b = 0.0;  // column total <= ub_a * max(m,i) + ub_b * p_ID * ib (model.cpp)
-    // nodes of the descendant hop entries (bh) per node, kept on the host for the run successors, and the run
-    // successors built so far, by run length (the plans of one model use few); model_upload drops them
+    // nodes of the descendant hop entries (bh) per node, kept on the host for the segment successors, and the
+    // successors built so far, by segment length (the plans of one model use few); model_upload drops them
     std::vector<uint32_t> desc_off, desc_node;
     std::mutex rs_mu;
     std::vector<std::unique_ptr<phmm::RunSucc>> rs_cache;
@@ -442,7 +443,7 @@ void refresh_knobs();
 
 void model_build_host(phmm_model *m);    // CSR + logib
 void model_upload(phmm_model *m);        // closures + device arrays
-const RunSucc &model_run_successors(phmm_model *m, int npt);  // built and uploaded on first use of a run length
+const RunSucc &model_run_successors(phmm_model *m, int seg);  // built and uploaded on first use of a segment length
 
 // dense driver (dense.hip)
 void run_dense(phmm_model *m, const phmm_reads *reads, double *out_lf, double *out_lb,

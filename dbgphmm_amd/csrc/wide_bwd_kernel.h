@@ -413,8 +413,8 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
             if (t < c.n) {
                 bm[(size_t)c.id[t] * a.W + r] = c.m[t];
                 bi[(size_t)c.id[t] * a.W + r] = c.i[t];
-                if (a.d.skH && (c.m[t] != 0.0 || c.i[t] != 0.0))  // (run skipping, dense.hip: the run counts from column s0 on)
-                    atomicOr(&a.d.skH[(size_t)g * a.d.nrun + c.id[t] / (uint32_t)a.d.npt], 1u << (s0 + 1 < 31 ? s0 + 1 : 31));
+                if (a.d.skH && (c.m[t] != 0.0 || c.i[t] != 0.0))  // (run skipping, dense.hip: the segment counts from column s0 on)
+                    atomicOr(&a.d.skH[(size_t)g * a.d.nseg + c.id[t] / (uint32_t)a.d.sseg], 1u << (s0 + 1 < 31 ? s0 + 1 : 31));
                 mx = fmax(c.m[t], c.i[t]);
             }
             mx = wb_block_max(sh, par, mx);
