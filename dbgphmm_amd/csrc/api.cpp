@@ -66,6 +66,7 @@ void refresh_knobs() {
     k.no_packed = flag("PHMM_NO_PACKED");
     k.packed_cpl = num("PHMM_PACKED_CPL", 0);
     k.no_exact_hinted = flag("PHMM_NO_EXACT_HINTED");
+    k.no_exact_dense = flag("PHMM_NO_EXACT_DENSE");
     k.no_wide_hinted = flag("PHMM_NO_WIDE_HINTED");
     k.wide_hinted = flag("PHMM_WIDE_HINTED") && !k.no_wide_hinted;
     k.wide_hinted_cpb = num("PHMM_WIDE_HINTED_CPB", 0);

@@ -1586,6 +1586,15 @@ void run_dense_impl(phmm_model *m, const uint8_t *bases, const uint64_t *off, ui
             for (uint32_t gi : flagged) ids.push_back(plan.order[(size_t)g0 * W + gi]);
             if (flagged_out) flagged_out->insert(flagged_out->end(), ids.begin(), ids.end());
             size_t j0 = 0;
+            if (knobs().no_exact_dense && !flagged_out) {
+                // PHMM_NO_EXACT_DENSE: show what the certificate decided instead of recomputing (a caller that takes
+                // the flagged list, phmm_dense_tables, decides for itself)
+                for (uint32_t id : ids) {
+                    lf[id] = NAN;
+                    if (want_b) lb[id] = NAN;
+                }
+                j0 = ids.size();
+            }
             while (j0 < ids.size()) {
                 size_t j1 = j0, bytes = 0;
                 while (j1 < ids.size()) {
@@ -1657,6 +1666,25 @@ void dense_tables(phmm_model *m, const uint8_t *read, uint64_t len, double *f_m,
     std::vector<uint32_t> flagged;
     run_dense_impl(m, one.bases.data(), one.off.data(), 1, plan, true, true, want_b, false, &lf, want_b ? &lb : nullptr,
                    nullptr, &a, nullptr, nullptr, &flagged);
+    if (flagged.empty()) {
+        // the read's P is certified; its single cells are another matter (exact_dense.hip: certify_dense_cells)
+        const int L = (int)len;
+        std::vector<int> hE((size_t)L + 1);
+        std::vector<unsigned long long> hc((size_t)L);
+        std::vector<double> mx((size_t)L);
+        auto cells_ok = [&](const int *E, const unsigned long long *cmax, bool backward) {
+            HIP_CHECK(hipMemcpyAsync(hE.data(), E, sizeof(int) * (L + 1), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(hc.data(), cmax, sizeof(unsigned long long) * L, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            for (int i = 0; i < L; i++) {
+                double v;
+                std::memcpy(&v, &hc[i], 8);
+                mx[i] = v > 0.0 ? std::log2(v) + hE[i] : -INFINITY;
+            }
+            return certify_dense_cells((int)m->N, L, hE.data(), mx.data(), backward);
+        };
+        if (!cells_ok(a.FE, a.cmaxF, false) || (want_b && !cells_ok(a.BE, a.cmaxB, true))) flagged.push_back(0);
+    }
     if (!flagged.empty()) {
         // outside the scaled range: the tables of the exact recursion instead (exact_dense.hip)
         ExactTables et{f_m, f_i, f_d, f_scal, b_m, b_i, b_d, b_scal};

@@ -108,5 +108,6 @@ void exact_dense_reads(phmm_model *m, const uint8_t *bases, const uint64_t *off,
                        double *init_freq_dev = nullptr);
 bool certify_dense(int N, int len, double log2P, const int *FE, const double *log2maxF, const int *BE, const double *log2maxB,
                    double log2_p_end);
+bool certify_dense_cells(int N, int len, const int *E, const double *log2max, bool backward);
 
 }  // namespace phmm

@@ -380,4 +380,24 @@ bool certify_dense(int N, int len, double log2P, const int *FE, const double *lo
     return true;
 }
 
+// Certificate of the single CELLS of one read's tables (phmm_dense_tables), one direction.  certify_dense bounds the
+// lost mass against P; a cell far below P can still be made of it.  What columns computed before column i lost
+// reaches any one cell of column i with at most 3 N len * 2^(max E_j - 1022 + slack); the cells the table bar speaks
+// of (within 600 nats of their column maximum, right to 1e-9) lie above
+// 2^(log2 max_i - 866 - 30).  Certified when the first stays below the second in every column: in effect, when no
+// column maximum lies more than ~28 nats below the scale of a column computed before it.  E / log2max: per column,
+// log2 of true values; backward: the columns are computed from the last one down.
+bool certify_dense_cells(int N, int len, const int *E, const double *log2max, bool backward) {
+    const double slack = 64.0;  // as in certify_dense
+    const double cells = std::log2(3.0 * (double)N * (double)std::max(len, 1)) + 1.0;
+    const double keep = 600.0 / std::log(2.0), prec = 30.0;
+    double emax = -INFINITY;
+    for (int c = 0; c < len; c++) {
+        const int i = backward ? len - 1 - c : c;
+        if (log2max[i] > -INFINITY && emax - 1022.0 + slack + cells > log2max[i] - keep - prec) return false;
+        emax = std::max(emax, (double)E[i]);
+    }
+    return true;
+}
+
 }  // namespace phmm

@@ -415,6 +415,8 @@ struct Knobs {
     bool no_packed = false;          // PHMM_NO_PACKED: one candidate per wave
     int packed_cpl = 0;              // PHMM_PACKED_CPL: candidates per lane (0: automatic)
     bool no_exact_hinted = false;    // PHMM_NO_EXACT_HINTED: no wide-range pass over reads that a candidate cuts
+    bool no_exact_dense = false;     // PHMM_NO_EXACT_DENSE: no log-domain pass over reads the dense certificate flags; their
+                                     // scores come back NaN and their posteriors are left out (phmm_dense_tables ignores it)
     bool wide_hinted = false;        // PHMM_WIDE_HINTED (and PHMM_NO_WIDE_HINTED unset): mapping lists of 65-400 nodes on a block
                                      // (hinted_wide_kernel.h).  Opt-in until it is timed against the generic kernels
     bool no_wide_hinted = false;     // PHMM_NO_WIDE_HINTED: generic kernels for mapping lists of 65-400 nodes (hinted forward)
