@@ -874,9 +874,104 @@ struct EvTimer {
     }
 };
 
-template <int CAP, int LPN> void launch_hinted(const HintedArgs &a, uint32_t n_reads, uint32_t n_cand) {
-    if (!n_reads) return;
-    hipLaunchKernelGGL((hinted_score_kernel<CAP, LPN>), dim3(n_reads, n_cand), dim3(64), 0, current_stream(), a);
+// The workspace slots of this file (WorkSet::aux, phmm_internal.h), by name.  A slot keeps its size across calls; what
+// it holds changes with the phase of a call, and a phase that takes a slot over starts behind a stream synchronisation
+// that ended the one before:
+//   WS_LISTS      hinted_run: the launch lists of the packed classes, then those of the wide classes (their cell
+//                 counter behind them), then the list of each generic class, then the pairs | results of the exact pass
+//   WS_CNC_MASKS  cnc_score: node (group) masks | read masks of a stateless call until they are read back, then (handle
+//                 calls too) pairs | gathered values | gathered error bits
+//   WS_CNC_LIST   cnc_score: the marks {candidate, node} until the masks are read back, then base vector | changes
+//   WS_STAGING    the caller's ln probabilities or copy-number vectors (the totals behind them) on their way to
+//                 WS_CAND_INIT / WS_CAND_TRANS
+//   WS_OUT        written by the hinted kernels; a handle's lk_compose / lk_commit read it after cnc_score
+//   WS_LK_MASKS   handle calls: as WS_CNC_MASKS' first phase, kept until lk_compose / lk_commit have run
+//   WS_LK_COMPOSE lk_run_compose: candidates | totals | [C][R] values; a move's change list behind that
+// mapping_flow.hip and sparse_dyn.hip use slots 13 and 14 as well, in calls that never overlap these.
+enum WsSlot {
+    WS_CAND_INIT = 7,    // [C][N] init of the candidates, linear
+    WS_CAND_TRANS = 8,   // [C][E] trans
+    WS_STAGING = 9,
+    WS_LISTS = 10,
+    WS_OUT = 11,         // [C][R] ln P planes
+    WS_ERR = 12,         // [C][R] error bits
+    WS_LK_MASKS = 13,
+    WS_LK_COMPOSE = 14,
+    WS_CNC_MASKS = 22,
+    WS_CNC_LIST = 23,
+};
+inline DevBuf &ws(phmm_model *m, WsSlot k) { return m->wset().aux[k]; }
+
+// ---- the scheduler of the score-only hinted forward (hinted_run, below the change form's kernels)
+// What a call scores.  Two shapes: the grid reads x planes (pairs == nullptr: the full form), or a list of
+// {read, plane} pairs, read-major (the touched pairs of the change form).  pair_off counts the pairs of a read in
+// either shape; which shape it is matters in hinted_list, hinted_errors and hinted_results only.
+struct HintedWork {
+    uint32_t planes = 0;      // candidates the kernels index: n_cand of the grid, the D dirty slots of a pair list
+    uint32_t call_cands = 0;  // candidates of the call, for the packed classes (the change form: its C, not D)
+    const uint64_t *pair_off = nullptr;  // [R + 1] first pair of each read (the grid: r x planes)
+    const uint2 *pairs = nullptr;        // host {read, plane}
+    const uint2 *d_pairs = nullptr;      // the pairs on the device, and room for a value and an error word each
+    double *d_res = nullptr;
+    uint32_t *d_rerr = nullptr;
+    const RecPool *pool = nullptr;  // forward records (forward_with_mapping): one-candidate kernels, no exact pass
+    bool scatter_exact = false;     // the planes are read after the call (a handle): the exact pass writes them too
+    double *vals = nullptr;         // out, host: [planes][R] of the grid, one value per pair of a list
+};
+// One class's reads as a launch: `n` blocks of `stride` words from word `at` of the uploaded lists, grid.y = y.
+// stride 1: a read id per block, its candidates by blockIdx.y (the kernels' plain form); above 1: work units
+// {read, stride - 1 planes}, 0xffffffff for an idle slot (their PAIRS form).
+struct HintedList {
+    size_t at;
+    unsigned n, y, stride;
+};
+
+// init_c / trans_c: [planes][N], [planes][E] linear; the result planes are reserved here
+HintedArgs hinted_args(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t planes,
+                       const double *init_c, const double *trans_c, const RecPool *pool) {
+    DevBuf &d_out = ws(m, WS_OUT), &d_err = ws(m, WS_ERR);
+    d_out.reserve((size_t)planes * reads->R * sizeof(double));
+    d_err.reserve((size_t)planes * reads->R * sizeof(uint32_t));
+    HintedArgs a{};
+    a.M = sparse_model(m);
+    a.init_c = init_c;
+    a.trans_c = trans_c;
+    a.E = m->E;
+    a.bases = reads->d_bases.as<uint8_t>();
+    a.read_off = reads->d_off.as<uint64_t>();
+    a.map_pos_off = mp->d_pos_off.as<uint64_t>();
+    a.map_nodes = mp->d_nodes.as<uint32_t>();
+    a.R = reads->R;
+    a.out_logp = d_out.as<double>();
+    a.err = d_err.as<uint32_t>();
+    if (pool) a.pool = *pool;
+    return a;
+}
+void hinted_run(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, HintedArgs a, const HintedWork &w);
+
+// packed class c (lists of at most 8 / 16 / 32 nodes), cpl candidates per lane
+template <bool PAIRS> void launch_hinted_packed(int c, int cpl, const HintedArgs &a, dim3 grid, uint32_t n_cand) {
+    hipStream_t s = current_stream();
+    if (cpl >= 2) {
+        if (c == 0) hipLaunchKernelGGL((hinted_packed_kernel<8, 2, PAIRS>), grid, dim3(64), 0, s, a, n_cand);
+        else if (c == 1) hipLaunchKernelGGL((hinted_packed_kernel<16, 2, PAIRS>), grid, dim3(64), 0, s, a, n_cand);
+        else hipLaunchKernelGGL((hinted_packed_kernel<32, 2, PAIRS>), grid, dim3(64), 0, s, a, n_cand);
+    } else {
+        if (c == 0) hipLaunchKernelGGL((hinted_packed_kernel<8, 1, PAIRS>), grid, dim3(64), 0, s, a, n_cand);
+        else if (c == 1) hipLaunchKernelGGL((hinted_packed_kernel<16, 1, PAIRS>), grid, dim3(64), 0, s, a, n_cand);
+        else hipLaunchKernelGGL((hinted_packed_kernel<32, 1, PAIRS>), grid, dim3(64), 0, s, a, n_cand);
+    }
+}
+// generic class c (lists of at most 64 / 128 / 400 nodes, 2 / 4 / 8 in-list parents per node), one wave per read and
+// candidate; lean: class 0 on graphs of degree <= ADJ_DEG, which also takes {read, plane} units
+void launch_hinted_generic(int c, bool lean, const HintedArgs &a, const HintedList &L) {
+    hipStream_t s = current_stream();
+    const dim3 grid(L.n, L.y);
+    if (lean && L.stride > 1) hipLaunchKernelGGL(hinted_lean_kernel<true>, grid, dim3(64), 0, s, a);
+    else if (lean) hipLaunchKernelGGL(hinted_lean_kernel<false>, grid, dim3(64), 0, s, a);
+    else if (c == 0) hipLaunchKernelGGL((hinted_score_kernel<64, 2>), grid, dim3(64), 0, s, a);
+    else if (c == 1) hipLaunchKernelGGL((hinted_score_kernel<128, 4>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hinted_score_kernel<400, 8>), grid, dim3(64), 0, s, a);
 }
 
 // hinted_wide_kernel: block class wc (0: lists of 65-128 nodes on 128 threads, 1: 129-400 on 448), cpb candidates per
@@ -972,6 +1067,25 @@ __global__ void __launch_bounds__(256) cn_probs(const uint32_t *cn, const uint8_
     }
 }
 
+namespace {
+// init / trans of the n_cand copy-number vectors d_cn [n_cand][N] into WS_CAND_INIT / WS_CAND_TRANS; d_tot: n_cand
+// zeroed words
+void copy_num_probs(phmm_model *m, const uint32_t *d_cn, uint32_t n_cand, uint32_t min_cn, unsigned long long *d_tot) {
+    hipStream_t s = current_stream();
+    const uint32_t N = m->N, E = m->E;
+    DevBuf &cand_init = ws(m, WS_CAND_INIT), &cand_trans = ws(m, WS_CAND_TRANS);
+    cand_init.reserve((size_t)n_cand * N * sizeof(double));
+    cand_trans.reserve(std::max<size_t>((size_t)n_cand * E, 1) * sizeof(double));
+    const unsigned nb = (unsigned)((N + 255) / 256);
+    hipLaunchKernelGGL(cn_totals, dim3(std::min(nb, 256u), n_cand), dim3(256), 0, s, d_cn, m->dev.emis.as<uint8_t>(), N, min_cn,
+                       d_tot);
+    hipLaunchKernelGGL(cn_probs, dim3(nb, n_cand), dim3(256), 0, s, d_cn, m->dev.emis.as<uint8_t>(),
+                       m->dev.chi_off.as<uint32_t>(), m->dev.chi_node.as<uint32_t>(), m->dev.chi_edge.as<uint32_t>(), N, E,
+                       min_cn, (const unsigned long long *)d_tot, cand_init.as<double>(), cand_trans.as<double>());
+    HIP_CHECK(hipGetLastError());
+}
+}  // namespace
+
 void full_prob_reads_hinted(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_cand,
                             const double *init_logp, const double *trans_logp, double *out_logp,
                             double *out_total, const RecPool *pool, const uint32_t *copy_nums, uint32_t min_copy_num) {
@@ -987,7 +1101,7 @@ void full_prob_reads_hinted(phmm_model *m, const phmm_reads *reads, const phmm_m
     ensure_logib(m, reads->max_len + 1);
 
     // candidate probabilities in the linear domain: [C][N], [C][E]
-    DevBuf &cand_init = m->wset().aux[7], &cand_trans = m->wset().aux[8], &staging = m->wset().aux[9];
+    DevBuf &cand_init = ws(m, WS_CAND_INIT), &cand_trans = ws(m, WS_CAND_TRANS), &staging = ws(m, WS_STAGING);
     const double *d_init = m->dev.init.as<double>();
     const double *d_trans = m->dev.trans_lin.as<double>();
     if (init_logp) {
@@ -1008,181 +1122,30 @@ void full_prob_reads_hinted(phmm_model *m, const phmm_reads *reads, const phmm_m
         d_init = cand_init.as<double>();
         d_trans = cand_trans.as<double>();
     } else if (copy_nums) {
-        const size_t ni = (size_t)n_cand * N, ne = (size_t)n_cand * E;
+        const size_t ni = (size_t)n_cand * N;
         staging.reserve(ni * sizeof(uint32_t) + 256 + n_cand * sizeof(unsigned long long));
-        cand_init.reserve(ni * sizeof(double));
-        cand_trans.reserve(std::max<size_t>(ne, 1) * sizeof(double));
         uint32_t *d_cn = staging.as<uint32_t>();
         unsigned long long *d_tot = (unsigned long long *)(staging.as<char>() + (ni * sizeof(uint32_t) + 255) / 256 * 256);
         HIP_CHECK(hipMemcpyAsync(d_cn, copy_nums, ni * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         HIP_CHECK(hipMemsetAsync(d_tot, 0, n_cand * sizeof(unsigned long long), s));
-        const unsigned nb = (unsigned)((N + 255) / 256);
-        hipLaunchKernelGGL(cn_totals, dim3(std::min(nb, 256u), n_cand), dim3(256), 0, s, d_cn, m->dev.emis.as<uint8_t>(), N,
-                           min_copy_num, d_tot);
-        hipLaunchKernelGGL(cn_probs, dim3(nb, n_cand), dim3(256), 0, s, d_cn, m->dev.emis.as<uint8_t>(),
-                           m->dev.chi_off.as<uint32_t>(), m->dev.chi_node.as<uint32_t>(), m->dev.chi_edge.as<uint32_t>(), N, E,
-                           min_copy_num, d_tot, cand_init.as<double>(), cand_trans.as<double>());
-        HIP_CHECK(hipGetLastError());
+        copy_num_probs(m, d_cn, n_cand, min_copy_num, d_tot);
         HIP_CHECK(hipStreamSynchronize(s));  // the caller's copy_nums may go away
         d_init = cand_init.as<double>();
         d_trans = cand_trans.as<double>();
     }
 
-    // capacity classes by the longest node list of each read.  Candidate batches: reads with short lists go to the
-    // packed kernels (several candidates per wave) first.
-    std::vector<uint32_t> cls[3], pcls[3], wcls[2];
-    uint64_t cells = 0;
-    const bool lean_ok = m->dev.max_degree <= (uint32_t)ADJ_DEG && !knobs().no_lean;
-    const bool packed_ok = n_cand >= 2 && !pool && lean_ok && !knobs().no_packed;
-    // lists of 65-400 nodes: one block per read (hinted_wide_kernel.h).  By the read's lists, the model and the knobs
-    // only -- never by n_cand: a batch stays bit-equal to one-candidate calls.  The class is opt-in (PHMM_WIDE_HINTED):
-    // it has not been timed against the generic kernels, and speed is its only purpose
-    const bool wide_ok = lean_ok && !pool && knobs().wide_hinted;
-    for (uint64_t r = 0; r < R; r++) {
-        const uint32_t mx = mp->read_max_list[r];
-        if (packed_ok && mx <= 32) pcls[mx <= 8 ? 0 : (mx <= 16 ? 1 : 2)].push_back((uint32_t)r);
-        else if (wide_ok && mx > 64 && mx <= HW_MAX_LIST) wcls[hinted_wide_class(mx)].push_back((uint32_t)r);
-        else cls[mx <= 64 ? 0 : (mx <= 128 ? 1 : 2)].push_back((uint32_t)r);
-    }
-    DevBuf &d_ids = m->wset().aux[10], &d_out = m->wset().aux[11], &d_err = m->wset().aux[12];
-    const size_t cells_at = (R * sizeof(uint32_t) + 7) / 8 * 8;  // (the cell counter of the wide class behind the ids)
-    d_ids.reserve(cells_at + sizeof(unsigned long long));
-    d_out.reserve((size_t)n_cand * R * sizeof(double));
-    d_err.reserve((size_t)n_cand * R * sizeof(uint32_t));
+    // the grid reads x candidates through the scheduler
     std::vector<double> h_out((size_t)n_cand * R);
-    std::vector<uint32_t> h_err((size_t)n_cand * R);
-
-    HintedArgs a{};
-    a.M = sparse_model(m);
-    a.init_c = d_init;
-    a.trans_c = d_trans;
-    a.E = E;
-    a.bases = reads->d_bases.as<uint8_t>();
-    a.read_off = reads->d_off.as<uint64_t>();
-    a.map_pos_off = mp->d_pos_off.as<uint64_t>();
-    a.map_nodes = mp->d_nodes.as<uint32_t>();
-    a.read_ids = d_ids.as<uint32_t>();
-    a.R = R;
-    a.out_logp = d_out.as<double>();
-    a.err = d_err.as<uint32_t>();
-    if (pool) a.pool = *pool;
-
+    std::vector<uint64_t> pair_off(R + 1);
+    for (uint64_t r = 0; r <= R; r++) pair_off[r] = r * n_cand;
+    HintedWork w;
+    w.planes = w.call_cands = n_cand;
+    w.pair_off = pair_off.data();
+    w.pool = pool;
+    w.vals = h_out.data();
+    const HintedArgs a = hinted_args(m, reads, mp, n_cand, d_init, d_trans, pool);
     EvTimer tm(timing_enabled());
-    for (int c = 0; c < 3; c++) {
-        if (pcls[c].empty()) continue;
-        HIP_CHECK(hipMemcpyAsync(d_ids.p, pcls[c].data(), pcls[c].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        const unsigned nr = (unsigned)pcls[c].size();
-        // candidates per wave = (64 / WG) x CPL; two per lane once a batch fills such waves
-        const int cpl_env = knobs().packed_cpl;
-        const int G = c == 0 ? 8 : (c == 1 ? 4 : 2);
-        const int cpl = cpl_env > 0 ? cpl_env : (n_cand >= (uint32_t)(2 * G) ? 2 : 1);
-        const unsigned per_wave = (unsigned)(G * (cpl >= 2 ? 2 : 1));
-        const dim3 grid(nr, (n_cand + per_wave - 1) / per_wave);
-        if (cpl >= 2) {
-            if (c == 0) hipLaunchKernelGGL((hinted_packed_kernel<8, 2>), grid, dim3(64), 0, s, a, n_cand);
-            else if (c == 1) hipLaunchKernelGGL((hinted_packed_kernel<16, 2>), grid, dim3(64), 0, s, a, n_cand);
-            else hipLaunchKernelGGL((hinted_packed_kernel<32, 2>), grid, dim3(64), 0, s, a, n_cand);
-        } else {
-            if (c == 0) hipLaunchKernelGGL((hinted_packed_kernel<8, 1>), grid, dim3(64), 0, s, a, n_cand);
-            else if (c == 1) hipLaunchKernelGGL((hinted_packed_kernel<16, 1>), grid, dim3(64), 0, s, a, n_cand);
-            else hipLaunchKernelGGL((hinted_packed_kernel<32, 1>), grid, dim3(64), 0, s, a, n_cand);
-        }
-        HIP_CHECK(hipGetLastError());
-        st.launches[2]++;
-        HIP_CHECK(hipMemcpyAsync(h_err.data(), d_err.p, h_err.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));  // (the read-id list is reused by the next class)
-        for (uint32_t rd : pcls[c]) {
-            uint32_t e = 0;
-            for (uint32_t k = 0; k < n_cand; k++) e |= h_err[(size_t)k * R + rd];
-            if (!e) continue;
-            if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
-            cls[0].push_back(rd);  // (cannot happen with read_max_list right: the one-candidate kernels take it)
-        }
-    }
-    if (!wcls[0].empty() || !wcls[1].empty()) {
-        EvTimer tw(timing_enabled());
-        unsigned long long *d_cells = (unsigned long long *)(d_ids.as<char>() + cells_at), h_cells = 0;
-        HIP_CHECK(hipMemsetAsync(d_cells, 0, sizeof(unsigned long long), s));
-        for (int wc = 0; wc < 2; wc++) {
-            if (wcls[wc].empty()) continue;
-            HIP_CHECK(hipMemcpyAsync(d_ids.p, wcls[wc].data(), wcls[wc].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            const int cpb = hinted_wide_cpb(wc, wcls[wc].size(), (uint64_t)wcls[wc].size() * n_cand);
-            launch_hinted_wide<false>(wc, cpb, a, dim3((unsigned)wcls[wc].size(), (n_cand + cpb - 1) / cpb), n_cand);
-            launch_hinted_wide_cells(a, (uint32_t)wcls[wc].size(), 1, n_cand, d_cells);
-            HIP_CHECK(hipGetLastError());
-            st.launches[2]++;
-            st.launches[4]++;
-            HIP_CHECK(hipMemcpyAsync(h_err.data(), d_err.p, h_err.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipMemcpyAsync(&h_cells, d_cells, sizeof(h_cells), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));  // (the read-id list is reused by the next class)
-            st.cells[4] = h_cells;  // (the counter runs over both classes)
-            for (uint32_t rd : wcls[wc]) {
-                uint32_t e = 0;
-                for (uint32_t k = 0; k < n_cand; k++) e |= h_err[(size_t)k * R + rd];
-                if (!e) continue;
-                if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
-                cls[mp->read_max_list[rd] <= 128 ? 1 : 2].push_back(rd);  // the generic kernel reports what it finds
-            }
-        }
-        st.ms[4] += tw.stop();
-    }
-    for (int c = 0; c < 3; c++) {
-        if (cls[c].empty()) continue;
-        HIP_CHECK(hipMemcpyAsync(d_ids.p, cls[c].data(), cls[c].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (c == 0 && lean_ok) {
-            hipLaunchKernelGGL(hinted_lean_kernel<false>, dim3((unsigned)cls[c].size(), n_cand), dim3(64), 0, s, a);
-        } else if (c == 0) launch_hinted<64, 2>(a, (uint32_t)cls[c].size(), n_cand);
-        else if (c == 1) launch_hinted<128, 4>(a, (uint32_t)cls[c].size(), n_cand);
-        else launch_hinted<400, 8>(a, (uint32_t)cls[c].size(), n_cand);
-        HIP_CHECK(hipGetLastError());
-        st.launches[2]++;
-        HIP_CHECK(hipMemcpyAsync(h_out.data(), d_out.p, h_out.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(h_err.data(), d_err.p, h_err.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        // reads whose in-list fan-in exceeded this class's link budget are promoted
-        for (uint32_t rd : cls[c]) {
-            uint32_t e = 0;
-            for (uint32_t k = 0; k < n_cand; k++) e |= h_err[(size_t)k * R + rd];
-            if (!e) continue;
-            if (e & SP_ERR_POOL) PHMM_THROW(PHMM_EINTERNAL, "forward record pool exhausted");
-            if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
-            if ((e & (SP_ERR_LINKS | SP_ERR_CAPACITY)) && c < 2) cls[c + 1].push_back(rd);
-            else PHMM_THROW(PHMM_ECAPACITY, "mapping list needs more than 400 slots / 8 in-list parents");
-        }
-    }
-    HIP_CHECK(hipMemcpyAsync(h_out.data(), d_out.p, h_out.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    // (candidate, read) pairs that came back -inf: the reference's InsBegin chain may still carry them (see
-    // hinted_exact_kernel) -- recomputed in its own arithmetic
-    if (!pool && !knobs().no_exact_hinted) {
-        std::vector<uint2> pairs;
-        for (uint32_t k = 0; k < n_cand; k++)
-            for (uint64_t r = 0; r < R; r++)
-                if (h_out[(size_t)k * R + r] == -INFINITY && reads->off[r + 1] > reads->off[r]) pairs.push_back(make_uint2(k, (uint32_t)r));
-        if (!pairs.empty()) {
-            // short lists first (the small kernel), the rest behind them
-            const size_t n_small = (size_t)(std::stable_partition(pairs.begin(), pairs.end(),
-                                                                  [&](const uint2 &q) { return mp->read_max_list[q.y] <= 64; }) -
-                                            pairs.begin());
-            DevBuf &d_pairs = m->wset().aux[10];  // (the read ids of the classes are spent)
-            d_pairs.reserve(pairs.size() * (sizeof(uint2) + sizeof(double)) + 256);
-            uint2 *dp = d_pairs.as<uint2>();
-            double *dres = (double *)(d_pairs.as<char>() + (pairs.size() * sizeof(uint2) + 255) / 256 * 256);
-            HIP_CHECK(hipMemcpyAsync(dp, pairs.data(), pairs.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
-            if (n_small)
-                hipLaunchKernelGGL((hinted_exact_kernel<64, 256>), dim3((unsigned)n_small), dim3(64), 0, s, a, (const uint2 *)dp, dres);
-            if (n_small < pairs.size())
-                hipLaunchKernelGGL((hinted_exact_kernel<PHMM_MAX_ACTIVE_NODES, 1024>), dim3((unsigned)(pairs.size() - n_small)),
-                                   dim3(64), 0, s, a, (const uint2 *)(dp + n_small), dres + n_small);
-            HIP_CHECK(hipGetLastError());
-            std::vector<double> hres(pairs.size());
-            HIP_CHECK(hipMemcpyAsync(hres.data(), dres, hres.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            for (size_t q = 0; q < pairs.size(); q++)
-                if (hres[q] == hres[q]) h_out[(size_t)pairs[q].x * R + pairs[q].y] = hres[q];
-            st.launches[2]++;
-        }
-    }
+    hinted_run(m, reads, mp, a, w);
     if (pool) {
         // generate_mappings WITH lists (forward + backward over the lists): the backward pass needs the forward columns
         // of the scaled kernels, which a read that every list node cuts (a k-mer at probability 0 on its path) does not
@@ -1195,8 +1158,7 @@ void full_prob_reads_hinted(phmm_model *m, const phmm_reads *reads, const phmm_m
                                             "use the non-zero PHMM (to_non_zero_phmm) for mapping, as the reference does");
     }
     st.ms[2] += tm.stop();
-    cells = mp->total_entries;
-    st.cells[2] = cells * n_cand;
+    st.cells[2] = mp->total_entries * n_cand;
 
     std::vector<double> tot(n_cand, 0.0);
     for (uint32_t k = 0; k < n_cand; k++)
@@ -1306,6 +1268,271 @@ __global__ void __launch_bounds__(256) cnc_scatter(const uint2 *pairs, const dou
 
 namespace {
 
+// ---------------------------------------------------------------- the scheduler of the score-only hinted forward
+// Which read goes to which kernel, what becomes of a read a kernel flags, and which pairs take the exact pass, for the
+// full form's grid and the change form's pair list alike (HintedWork).
+
+// Generic class of a longest list of mx nodes
+inline int hinted_generic_class(uint32_t mx) { return mx <= 64 ? 0 : (mx <= 128 ? 1 : 2); }
+
+// The reads `rds` of one class as a launch, appended to `words`.  The grid, and the generic kernels in either shape
+// (whole_reads), take the read ids x ceil(planes / per_unit) in y; a pair list becomes work units of per_unit planes.
+// The generic kernels run over a class's reads x every plane and only the pairs are read back: a pair-list instantiation
+// of hinted_score_kernel would change the register allocation of the shared fwd_list_step in the reads x candidates
+// one, and a launch per candidate serialises long reads.
+HintedList hinted_list(const HintedWork &w, const std::vector<uint32_t> &rds, unsigned per_unit, bool whole_reads,
+                       std::vector<uint32_t> &words) {
+    HintedList L{words.size(), 0, 1, 1};
+    if (!w.pairs || whole_reads) {
+        words.insert(words.end(), rds.begin(), rds.end());
+        L.n = (unsigned)rds.size();
+        L.y = (w.planes + per_unit - 1) / per_unit;
+        return L;
+    }
+    L.stride = 1 + per_unit;
+    for (uint32_t r : rds)
+        for (uint64_t q = w.pair_off[r]; q < w.pair_off[r + 1]; q += per_unit) {
+            words.push_back(r);
+            for (unsigned k = 0; k < per_unit; k++)
+                words.push_back(q + k < w.pair_off[r + 1] ? w.pairs[q + k].y : 0xffffffffu);
+        }
+    L.n = (unsigned)((words.size() - L.at) / L.stride);
+    return L;
+}
+
+void launch_cnc_gather(const HintedArgs &a, const HintedWork &w) {
+    const size_t n = w.pair_off[a.R];
+    hipLaunchKernelGGL(cnc_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, current_stream(), w.d_pairs, n, a.R,
+                       (const double *)a.out_logp, (const uint32_t *)a.err, w.d_res, w.d_rerr);
+    HIP_CHECK(hipGetLastError());
+}
+
+// Once the launches before it have finished: the error bits of every read of the n_lists class lists, OR-ed over the
+// read's candidates, in list order
+void hinted_errors(const HintedArgs &a, const HintedWork &w, const std::vector<uint32_t> *lists, int n_lists,
+                   std::vector<uint32_t> &h_err, std::vector<uint32_t> &read_err) {
+    hipStream_t s = current_stream();
+    const uint64_t R = a.R;
+    read_err.clear();
+    if (!w.pairs) {
+        h_err.resize((size_t)w.planes * R);
+        HIP_CHECK(hipMemcpyAsync(h_err.data(), a.err, h_err.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        for (int c = 0; c < n_lists; c++)
+            for (uint32_t rd : lists[c]) {
+                uint32_t e = 0;
+                for (uint32_t k = 0; k < w.planes; k++) e |= h_err[(size_t)k * R + rd];
+                read_err.push_back(e);
+            }
+        return;
+    }
+    h_err.resize(w.pair_off[R]);
+    launch_cnc_gather(a, w);
+    HIP_CHECK(hipMemcpyAsync(h_err.data(), w.d_rerr, h_err.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (int c = 0; c < n_lists; c++)
+        for (uint32_t rd : lists[c]) {
+            uint32_t e = 0;
+            for (uint64_t q = w.pair_off[rd]; q < w.pair_off[rd + 1]; q++) e |= h_err[q];
+            read_err.push_back(e);
+        }
+}
+
+// What becomes of a read whose error bits are e: nothing (-1), the generic class that takes it next, or a throw.
+// stage 0: a packed class flagged it, 1: a wide class, 2: the generic class c.
+int hinted_route(uint32_t e, int stage, int c, uint32_t max_list) {
+    if (!e) return -1;
+    if (e & SP_ERR_POOL) PHMM_THROW(PHMM_EINTERNAL, "forward record pool exhausted");
+    if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
+    if (stage == 0) return 0;  // (cannot happen with read_max_list right: the one-candidate kernels take it)
+    if (stage == 1) return hinted_generic_class(max_list);  // the generic kernel reports what it finds
+    // reads whose in-list fan-in exceeded this class's link budget are promoted
+    if ((e & (SP_ERR_LINKS | SP_ERR_CAPACITY)) && c < 2) return c + 1;
+    PHMM_THROW(PHMM_ECAPACITY, "mapping list needs more than 400 slots / 8 in-list parents");
+}
+
+// A pair that came back -inf, and where its value lives in w.vals
+struct HintedCut {
+    uint32_t plane, read;
+    size_t at;
+};
+// The values of the call into w.vals; the -inf pairs of non-empty reads in `cut`, in the order of w.vals
+void hinted_results(const HintedArgs &a, const HintedWork &w, const phmm_reads *reads, std::vector<HintedCut> &cut) {
+    hipStream_t s = current_stream();
+    const uint64_t R = a.R;
+    if (!w.pairs) {
+        HIP_CHECK(hipMemcpyAsync(w.vals, a.out_logp, (size_t)w.planes * R * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        for (uint32_t k = 0; k < w.planes; k++)
+            for (uint64_t r = 0; r < R; r++)
+                if (w.vals[(size_t)k * R + r] == -INFINITY && reads->off[r + 1] > reads->off[r])
+                    cut.push_back(HintedCut{k, (uint32_t)r, (size_t)k * R + r});
+        return;
+    }
+    const size_t n = w.pair_off[R];  // (pairs of non-empty reads only)
+    launch_cnc_gather(a, w);
+    HIP_CHECK(hipMemcpyAsync(w.vals, w.d_res, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t q = 0; q < n; q++)
+        if (w.vals[q] == -INFINITY) cut.push_back(HintedCut{w.pairs[q].y, w.pairs[q].x, q});
+}
+
+// (candidate, read) pairs that came back -inf: the reference's InsBegin chain may still carry them (see
+// hinted_exact_kernel) -- recomputed in its own arithmetic
+void hinted_exact_pass(phmm_model *m, const phmm_mappings *mp, const HintedArgs &a, const HintedWork &w,
+                       std::vector<HintedCut> &cut) {
+    if (cut.empty()) return;
+    hipStream_t s = current_stream();
+    // short lists first (the small kernel), the rest behind them
+    const size_t n = cut.size();
+    const size_t n_small = (size_t)(std::stable_partition(cut.begin(), cut.end(), [&](const HintedCut &q) {
+                                        return mp->read_max_list[q.read] <= 64;
+                                    }) - cut.begin());
+    std::vector<uint2> xs(n);  // {plane, read}
+    for (size_t i = 0; i < n; i++) xs[i] = make_uint2(cut[i].plane, cut[i].read);
+    DevBuf &buf = ws(m, WS_LISTS);  // (the launch lists are spent)
+    const size_t res_at = (n * sizeof(uint2) + 255) / 256 * 256;
+    buf.reserve(res_at + n * sizeof(double));
+    uint2 *dp = buf.as<uint2>();
+    double *dres = (double *)(buf.as<char>() + res_at);
+    HIP_CHECK(hipMemcpyAsync(dp, xs.data(), n * sizeof(uint2), hipMemcpyHostToDevice, s));
+    if (n_small)
+        hipLaunchKernelGGL((hinted_exact_kernel<64, 256>), dim3((unsigned)n_small), dim3(64), 0, s, a, (const uint2 *)dp, dres);
+    if (n_small < n)
+        hipLaunchKernelGGL((hinted_exact_kernel<PHMM_MAX_ACTIVE_NODES, 1024>), dim3((unsigned)(n - n_small)), dim3(64), 0, s,
+                           a, (const uint2 *)(dp + n_small), dres + n_small);
+    if (w.scatter_exact)
+        hipLaunchKernelGGL(cnc_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint2 *)dp,
+                           (const double *)dres, n, a.R, a.out_logp);
+    HIP_CHECK(hipGetLastError());
+    std::vector<double> hres(n);
+    HIP_CHECK(hipMemcpyAsync(hres.data(), dres, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; i++)
+        if (hres[i] == hres[i]) w.vals[cut[i].at] = hres[i];
+    stats().launches[2]++;
+}
+
+void hinted_run(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, HintedArgs a, const HintedWork &w) {
+    hipStream_t s = current_stream();
+    CallStats &st = stats();
+    const uint64_t R = reads->R;
+    DevBuf &d_lists = ws(m, WS_LISTS);
+    // capacity classes by the longest node list of each read.  Candidate batches: reads with short lists go to the
+    // packed kernels (several candidates per wave) first.
+    const bool lean_ok = m->dev.max_degree <= (uint32_t)ADJ_DEG && !knobs().no_lean;
+    const bool packed_ok = w.call_cands >= 2 && !w.pool && lean_ok && !knobs().no_packed;
+    // lists of 65-400 nodes: one block per read (hinted_wide_kernel.h).  By the read's lists, the model and the knobs
+    // only -- never by the candidate count: a batch stays bit-equal to one-candidate calls.  The class is opt-in
+    // (PHMM_WIDE_HINTED): it has not been timed against the generic kernels, and speed is its only purpose
+    const bool wide_ok = lean_ok && !w.pool && knobs().wide_hinted;
+    std::vector<uint32_t> cls[3], pcls[3], wcls[2];
+    for (uint64_t r = 0; r < R; r++) {
+        if (w.pair_off[r + 1] == w.pair_off[r]) continue;
+        const uint32_t mx = mp->read_max_list[r];
+        if (packed_ok && mx <= 32) pcls[mx <= 8 ? 0 : (mx <= 16 ? 1 : 2)].push_back((uint32_t)r);
+        else if (wide_ok && mx > 64 && mx <= HW_MAX_LIST) wcls[hinted_wide_class(mx)].push_back((uint32_t)r);
+        else cls[hinted_generic_class(mx)].push_back((uint32_t)r);
+    }
+    auto class_pairs = [&](const std::vector<uint32_t> &rds) {
+        uint64_t np = 0;
+        for (uint32_t r : rds) np += w.pair_off[r + 1] - w.pair_off[r];
+        return np;
+    };
+    std::vector<uint32_t> words, h_err, read_err;
+    HintedList L[3];
+
+    // packed classes: candidates per wave = (64 / WG) x CPL; two per lane once a class has that many pairs per read
+    // on average.  The three classes behind one upload.
+    int cpl[3];
+    for (int c = 0; c < 3; c++) {
+        const int G = c == 0 ? 8 : (c == 1 ? 4 : 2);
+        const int cpl_env = knobs().packed_cpl;
+        cpl[c] = (cpl_env > 0 ? cpl_env >= 2 : class_pairs(pcls[c]) >= (uint64_t)(2 * G) * pcls[c].size()) ? 2 : 1;
+        L[c] = hinted_list(w, pcls[c], (unsigned)(G * cpl[c]), false, words);
+    }
+    if (!words.empty()) {
+        d_lists.reserve(words.size() * sizeof(uint32_t));
+        HIP_CHECK(hipMemcpyAsync(d_lists.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        for (int c = 0; c < 3; c++) {
+            if (!L[c].n) continue;
+            a.read_ids = d_lists.as<uint32_t>() + L[c].at;
+            if (L[c].stride > 1) launch_hinted_packed<true>(c, cpl[c], a, dim3(L[c].n, L[c].y), w.planes);
+            else launch_hinted_packed<false>(c, cpl[c], a, dim3(L[c].n, L[c].y), w.planes);
+            HIP_CHECK(hipGetLastError());
+            st.launches[2]++;
+        }
+        hinted_errors(a, w, pcls, 3, h_err, read_err);
+        size_t i = 0;
+        for (int c = 0; c < 3; c++)
+            for (uint32_t rd : pcls[c])
+                if (hinted_route(read_err[i++], 0, c, 0) >= 0) cls[0].push_back(rd);
+    }
+    trace("hinted: packed classes");
+    // wide lists (65-400 nodes): the two classes behind one upload, the cell counter of the call statistics behind them
+    if (!wcls[0].empty() || !wcls[1].empty()) {
+        EvTimer tw(timing_enabled());
+        words.clear();
+        int cpb[2];
+        for (int wc = 0; wc < 2; wc++) {
+            cpb[wc] = hinted_wide_cpb(wc, wcls[wc].size(), class_pairs(wcls[wc]));
+            L[wc] = hinted_list(w, wcls[wc], (unsigned)cpb[wc], false, words);
+        }
+        const size_t cells_at = (words.size() * sizeof(uint32_t) + 7) / 8 * 8;
+        d_lists.reserve(cells_at + sizeof(unsigned long long));
+        unsigned long long *d_cells = (unsigned long long *)(d_lists.as<char>() + cells_at), h_cells = 0;
+        HIP_CHECK(hipMemcpyAsync(d_lists.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetAsync(d_cells, 0, sizeof(unsigned long long), s));
+        for (int wc = 0; wc < 2; wc++) {
+            if (!L[wc].n) continue;
+            a.read_ids = d_lists.as<uint32_t>() + L[wc].at;
+            if (L[wc].stride > 1) launch_hinted_wide<true>(wc, cpb[wc], a, dim3(L[wc].n, L[wc].y), w.planes);
+            else launch_hinted_wide<false>(wc, cpb[wc], a, dim3(L[wc].n, L[wc].y), w.planes);
+            launch_hinted_wide_cells(a, L[wc].n, L[wc].stride, w.planes, d_cells);
+            HIP_CHECK(hipGetLastError());
+            st.launches[2]++;
+            st.launches[4]++;
+        }
+        HIP_CHECK(hipMemcpyAsync(&h_cells, d_cells, sizeof(h_cells), hipMemcpyDeviceToHost, s));
+        hinted_errors(a, w, wcls, 2, h_err, read_err);
+        st.cells[4] += h_cells;
+        size_t i = 0;
+        for (int wc = 0; wc < 2; wc++)
+            for (uint32_t rd : wcls[wc]) {
+                const int to = hinted_route(read_err[i++], 1, wc, mp->read_max_list[rd]);
+                if (to >= 0) cls[to].push_back(rd);
+            }
+        st.ms[4] += tw.stop();
+    }
+    trace("hinted: wide classes");
+    // one-candidate classes, a launch and a read-back each: a read any of whose candidates overflows a class is
+    // appended to the next one.  Class 0 runs the lean kernel where the graph allows it; the generic kernels take what
+    // the lean and the wide class do not (degree above ADJ_DEG, PHMM_NO_LEAN set, lists over 64 nodes while the wide
+    // class is not switched on, or a read one of them flagged).
+    for (int c = 0; c < 3; c++) {
+        if (cls[c].empty()) continue;
+        const bool lean = c == 0 && lean_ok;
+        words.clear();
+        const HintedList Lc = hinted_list(w, cls[c], 1, !lean, words);
+        d_lists.reserve(words.size() * sizeof(uint32_t));
+        HIP_CHECK(hipMemcpyAsync(d_lists.p, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        a.read_ids = d_lists.as<uint32_t>();
+        launch_hinted_generic(c, lean, a, Lc);
+        HIP_CHECK(hipGetLastError());
+        st.launches[2]++;
+        hinted_errors(a, w, &cls[c], 1, h_err, read_err);
+        for (size_t i = 0; i < read_err.size(); i++) {
+            const int to = hinted_route(read_err[i], 2, c, 0);
+            if (to >= 0) cls[to].push_back(cls[c][i]);
+        }
+    }
+    std::vector<HintedCut> cut;
+    hinted_results(a, w, reads, cut);
+    trace("hinted: one-candidate classes");
+    if (!w.pool && !knobs().no_exact_hinted) hinted_exact_pass(m, mp, a, w, cut);
+    trace("hinted: exact pass");
+}
+
 // One batch of candidates against a base vector: which (read, candidate) pairs are rescored, and their values.
 // The stateless entry point composes its outputs from this on the host (its bits are pinned by its tests); a
 // phmm_likelihood handle brings the base vector on the device and composes on the device.
@@ -1318,7 +1545,7 @@ struct CncJob {
     const uint64_t *chg_off = nullptr;
     const uint32_t *chg_node = nullptr, *chg_cn = nullptr;
     const phmm_likelihood *grp = nullptr;  // chg_node holds group ids of this handle (uniform groups, checked by the caller)
-    bool on_device = false;  // keep the read masks (aux[13]) and every final value in the [D][R] planes (aux[11])
+    bool on_device = false;  // keep the read masks (WS_LK_MASKS) and every final value in the [D][R] planes (WS_OUT)
     // out
     std::vector<uint8_t> full;       // [C] no finite shift: every non-empty read is rescored
     std::vector<uint64_t> Tc;        // [C]
@@ -1333,7 +1560,7 @@ struct CncJob {
 void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, CncJob &job) {
     hipStream_t s = current_stream();
     const uint64_t R = reads->R;
-    const uint32_t N = m->N, E = m->E;
+    const uint32_t N = m->N;
     const uint8_t *emis = m->emission.data();
     const uint32_t *base_cn = job.base_cn, min_cn = job.min_cn, C = job.C;
     const uint64_t *chg_off = job.chg_off;
@@ -1379,8 +1606,8 @@ void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, 
     // read masks: bit c % 64 of word c / 64 set when the read's lists meet A_c
     const uint32_t W = (C + 63) / 64;
     std::vector<unsigned long long> rmask((size_t)W * R, 0ull);
-    DevBuf &d_mask = m->wset().aux[22], &d_list = m->wset().aux[23];
-    DevBuf &d_nrmask = job.on_device ? m->wset().aux[13] : d_mask;  // (d_mask takes the pairs below)
+    DevBuf &d_mask = ws(m, WS_CNC_MASKS), &d_list = ws(m, WS_CNC_LIST);
+    DevBuf &d_nrmask = job.on_device ? ws(m, WS_LK_MASKS) : d_mask;  // (d_mask takes the pairs below)
     if (job.on_device) {
         d_nrmask.reserve((size_t)W * S * 8 + (size_t)W * R * 8);
         unsigned long long *rm = d_nrmask.as<unsigned long long>() + (size_t)W * S;
@@ -1455,16 +1682,14 @@ void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, 
     if (D) {
         // init / trans of the D dirty candidates: the base vector plus their changes, then the full form's cn_totals /
         // cn_probs -- the same probabilities, bit for bit
-        DevBuf &cand_init = m->wset().aux[7], &cand_trans = m->wset().aux[8], &staging = m->wset().aux[9];
+        DevBuf &staging = ws(m, WS_STAGING);
         std::vector<uint3> apply;
         for (uint32_t d = 0; d < D; d++)
             for (uint64_t j = chg_off[cand_of[d]]; j < chg_off[cand_of[d] + 1]; j++)
                 apply.push_back(make_uint3(d, chg_node[j], chg_cn[j]));
-        const size_t ni = (size_t)D * N, ne = (size_t)D * E;
+        const size_t ni = (size_t)D * N;
         const size_t tot_at = (ni * sizeof(uint32_t) + 255) / 256 * 256;
         staging.reserve(tot_at + D * sizeof(unsigned long long));
-        cand_init.reserve(ni * sizeof(double));
-        cand_trans.reserve(std::max<size_t>(ne, 1) * sizeof(double));
         const size_t apply_at = ((size_t)N * sizeof(uint32_t) + 255) / 256 * 256;
         d_list.reserve(apply_at + std::max<size_t>(apply.size(), 1) * sizeof(uint3));
         const uint32_t *d_base = job.d_base ? job.d_base : d_list.as<uint32_t>();
@@ -1484,238 +1709,29 @@ void cnc_score(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, 
         else if (!apply.empty())
             hipLaunchKernelGGL(cnc_apply, dim3((unsigned)((apply.size() + 255) / 256)), dim3(256), 0, s,
                                (const uint3 *)d_apply, (uint32_t)apply.size(), N, d_cn);
-        hipLaunchKernelGGL(cn_totals, dim3(std::min(nb, 256u), D), dim3(256), 0, s, (const uint32_t *)d_cn,
-                           m->dev.emis.as<uint8_t>(), N, min_cn, d_tot);
-        hipLaunchKernelGGL(cn_probs, dim3(nb, D), dim3(256), 0, s, (const uint32_t *)d_cn, m->dev.emis.as<uint8_t>(),
-                           m->dev.chi_off.as<uint32_t>(), m->dev.chi_node.as<uint32_t>(), m->dev.chi_edge.as<uint32_t>(), N, E,
-                           min_cn, (const unsigned long long *)d_tot, cand_init.as<double>(), cand_trans.as<double>());
-        HIP_CHECK(hipGetLastError());
+        copy_num_probs(m, d_cn, D, min_cn, d_tot);
         trace("cnc: expand + cn_probs");
 
-        // the pairs, and the [D][R] result planes of the kernels
-        DevBuf &d_ids = m->wset().aux[10], &d_out = m->wset().aux[11], &d_err = m->wset().aux[12];
-        d_out.reserve((size_t)D * R * sizeof(double));
-        d_err.reserve((size_t)D * R * sizeof(uint32_t));
+        // the pairs on the device, a value and an error word each behind them, and through the scheduler: the kernels
+        // write [D][R] planes
         const size_t res_at = (pairs.size() * sizeof(uint2) + 255) / 256 * 256;
         const size_t rerr_at = res_at + (pairs.size() * sizeof(double) + 255) / 256 * 256;
         d_mask.reserve(rerr_at + pairs.size() * sizeof(uint32_t));  // (the masks are spent)
-        uint2 *d_pairs = d_mask.as<uint2>();
-        double *d_res = (double *)(d_mask.as<char>() + res_at);
-        uint32_t *d_rerr = (uint32_t *)(d_mask.as<char>() + rerr_at);
-        HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
-        std::vector<uint32_t> rerr(pairs.size());
-        auto gather = [&](bool values) {
-            hipLaunchKernelGGL(cnc_gather, dim3((unsigned)((pairs.size() + 255) / 256)), dim3(256), 0, s,
-                               (const uint2 *)d_pairs, pairs.size(), R, (const double *)d_out.as<double>(),
-                               (const uint32_t *)d_err.as<uint32_t>(), d_res, d_rerr);
-            HIP_CHECK(hipGetLastError());
-            if (values) HIP_CHECK(hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipMemcpyAsync(rerr.data(), d_rerr, rerr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-        };
-
-        HintedArgs a{};
-        a.M = sparse_model(m);
-        a.init_c = cand_init.as<double>();
-        a.trans_c = cand_trans.as<double>();
-        a.E = E;
-        a.bases = reads->d_bases.as<uint8_t>();
-        a.read_off = reads->d_off.as<uint64_t>();
-        a.map_pos_off = mp->d_pos_off.as<uint64_t>();
-        a.map_nodes = mp->d_nodes.as<uint32_t>();
-        a.R = R;
-        a.out_logp = d_out.as<double>();
-        a.err = d_err.as<uint32_t>();
-
-        // capacity classes by the longest list of each read, as full_prob_reads_hinted has them
-        const bool lean_ok = m->dev.max_degree <= (uint32_t)ADJ_DEG && !knobs().no_lean;
-        const bool packed_ok = C >= 2 && lean_ok && !knobs().no_packed;
-        const bool wide_ok = lean_ok && knobs().wide_hinted;
-        std::vector<uint32_t> cls[3], pcls[3], wcls[2];
-        for (uint64_t r = 0; r < R; r++) {
-            if (read_pair_off[r + 1] == read_pair_off[r]) continue;
-            const uint32_t mx = mp->read_max_list[r];
-            if (packed_ok && mx <= 32) pcls[mx <= 8 ? 0 : (mx <= 16 ? 1 : 2)].push_back((uint32_t)r);
-            else if (wide_ok && mx > 64 && mx <= HW_MAX_LIST) wcls[hinted_wide_class(mx)].push_back((uint32_t)r);
-            else cls[mx <= 64 ? 0 : (mx <= 128 ? 1 : 2)].push_back((uint32_t)r);
-        }
-        // packed classes: work units {read, G x CPL slots}, the three classes behind one upload
-        std::vector<uint32_t> units;
-        size_t unit_at[3], n_units[3];
-        int cpls[3];
-        for (int c = 0; c < 3; c++) {
-            const int G = c == 0 ? 8 : (c == 1 ? 4 : 2);
-            uint64_t np = 0;
-            for (uint32_t r : pcls[c]) np += read_pair_off[r + 1] - read_pair_off[r];
-            const int cpl_env = knobs().packed_cpl;
-            cpls[c] = cpl_env > 0 ? (cpl_env >= 2 ? 2 : 1) : (np >= (uint64_t)(2 * G) * pcls[c].size() ? 2 : 1);
-            const int pw = G * cpls[c];
-            unit_at[c] = units.size();
-            for (uint32_t r : pcls[c])
-                for (uint64_t q = read_pair_off[r]; q < read_pair_off[r + 1]; q += pw) {
-                    units.push_back(r);
-                    for (int k = 0; k < pw; k++) units.push_back(q + k < read_pair_off[r + 1] ? pairs[q + k].y : 0xffffffffu);
-                }
-            n_units[c] = (units.size() - unit_at[c]) / (size_t)(1 + pw);
-        }
-        if (!units.empty()) {
-            d_ids.reserve(units.size() * sizeof(uint32_t));
-            HIP_CHECK(hipMemcpyAsync(d_ids.p, units.data(), units.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            for (int c = 0; c < 3; c++) {
-                if (!n_units[c]) continue;
-                HintedArgs au = a;
-                au.read_ids = d_ids.as<uint32_t>() + unit_at[c];
-                const dim3 grid((unsigned)n_units[c]);
-                if (cpls[c] >= 2) {
-                    if (c == 0) hipLaunchKernelGGL((hinted_packed_kernel<8, 2, true>), grid, dim3(64), 0, s, au, D);
-                    else if (c == 1) hipLaunchKernelGGL((hinted_packed_kernel<16, 2, true>), grid, dim3(64), 0, s, au, D);
-                    else hipLaunchKernelGGL((hinted_packed_kernel<32, 2, true>), grid, dim3(64), 0, s, au, D);
-                } else {
-                    if (c == 0) hipLaunchKernelGGL((hinted_packed_kernel<8, 1, true>), grid, dim3(64), 0, s, au, D);
-                    else if (c == 1) hipLaunchKernelGGL((hinted_packed_kernel<16, 1, true>), grid, dim3(64), 0, s, au, D);
-                    else hipLaunchKernelGGL((hinted_packed_kernel<32, 1, true>), grid, dim3(64), 0, s, au, D);
-                }
-                HIP_CHECK(hipGetLastError());
-                stats().launches[2]++;
-            }
-            gather(false);
-            for (int c = 0; c < 3; c++)
-                for (uint32_t rd : pcls[c]) {
-                    uint32_t e = 0;
-                    for (uint64_t q = read_pair_off[rd]; q < read_pair_off[rd + 1]; q++) e |= rerr[q];
-                    if (!e) continue;
-                    if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
-                    cls[0].push_back(rd);
-                }
-        }
-        trace("cnc: packed classes");
-        // wide lists (65-400 nodes): work units {read, cpb slots}, only the touched pairs (hinted_wide_kernel.h)
-        if (!wcls[0].empty() || !wcls[1].empty()) {
-            EvTimer tw(timing_enabled());
-            std::vector<uint32_t> wu;
-            size_t wu_at[2], wu_n[2];
-            int wcpb[2];
-            for (int wc = 0; wc < 2; wc++) {
-                uint64_t np = 0;
-                for (uint32_t r : wcls[wc]) np += read_pair_off[r + 1] - read_pair_off[r];
-                wcpb[wc] = hinted_wide_cpb(wc, wcls[wc].size(), np);
-                wu_at[wc] = wu.size();
-                for (uint32_t r : wcls[wc])
-                    for (uint64_t q = read_pair_off[r]; q < read_pair_off[r + 1]; q += wcpb[wc]) {
-                        wu.push_back(r);
-                        for (int k = 0; k < wcpb[wc]; k++)
-                            wu.push_back(q + k < read_pair_off[r + 1] ? pairs[q + k].y : 0xffffffffu);
-                    }
-                wu_n[wc] = (wu.size() - wu_at[wc]) / (size_t)(1 + wcpb[wc]);
-            }
-            const size_t cells_at = (wu.size() * sizeof(uint32_t) + 7) / 8 * 8;  // (the cell counter behind the units)
-            d_ids.reserve(cells_at + sizeof(unsigned long long));
-            unsigned long long *d_cells = (unsigned long long *)(d_ids.as<char>() + cells_at), h_cells = 0;
-            HIP_CHECK(hipMemcpyAsync(d_ids.p, wu.data(), wu.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            HIP_CHECK(hipMemsetAsync(d_cells, 0, sizeof(unsigned long long), s));
-            for (int wc = 0; wc < 2; wc++) {
-                if (!wu_n[wc]) continue;
-                HintedArgs au = a;
-                au.read_ids = d_ids.as<uint32_t>() + wu_at[wc];
-                launch_hinted_wide<true>(wc, wcpb[wc], au, dim3((unsigned)wu_n[wc]), D);
-                launch_hinted_wide_cells(au, (uint32_t)wu_n[wc], (uint32_t)(1 + wcpb[wc]), 0, d_cells);
-                HIP_CHECK(hipGetLastError());
-                stats().launches[2]++;
-                stats().launches[4]++;
-            }
-            HIP_CHECK(hipMemcpyAsync(&h_cells, d_cells, sizeof(h_cells), hipMemcpyDeviceToHost, s));
-            gather(false);
-            stats().cells[4] += h_cells;
-            for (int wc = 0; wc < 2; wc++)
-                for (uint32_t rd : wcls[wc]) {
-                    uint32_t e = 0;
-                    for (uint64_t q = read_pair_off[rd]; q < read_pair_off[rd + 1]; q++) e |= rerr[q];
-                    if (!e) continue;
-                    if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
-                    cls[mp->read_max_list[rd] <= 128 ? 1 : 2].push_back(rd);
-                }
-            stats().ms[4] += tw.stop();
-        }
-        trace("cnc: wide classes");
-        // one-candidate classes; a read any of whose pairs overflows a class is promoted.  The lean class takes one
-        // {read, slot} pair per wave.  The generic kernels (what the lean and the wide class do not take: degree above ADJ_DEG,
-        // PHMM_NO_LEAN set, lists over 64 nodes while the wide class is not switched on, or a read one of them flagged) run
-        // as in the full form, over the class's reads x the D candidates, and only the pairs are read back: a pair-list
-        // instantiation of hinted_score_kernel would change the register allocation of the shared fwd_list_step in the
-        // reads x candidates one, and a launch per candidate serialises long reads.
-        std::vector<uint32_t> wl;
-        for (int c = 0; c < 3; c++) {
-            if (cls[c].empty()) continue;
-            wl.clear();
-            if (c == 0 && lean_ok) {
-                for (uint32_t rd : cls[c])
-                    for (uint64_t q = read_pair_off[rd]; q < read_pair_off[rd + 1]; q++) {
-                        wl.push_back(pairs[q].x);
-                        wl.push_back(pairs[q].y);
-                    }
-                d_ids.reserve(wl.size() * sizeof(uint32_t));
-                HIP_CHECK(hipMemcpyAsync(d_ids.p, wl.data(), wl.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-                a.read_ids = d_ids.as<uint32_t>();
-                hipLaunchKernelGGL(hinted_lean_kernel<true>, dim3((unsigned)(wl.size() / 2)), dim3(64), 0, s, a);
-            } else {
-                d_ids.reserve(cls[c].size() * sizeof(uint32_t));
-                HIP_CHECK(hipMemcpyAsync(d_ids.p, cls[c].data(), cls[c].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-                a.read_ids = d_ids.as<uint32_t>();
-                if (c == 0) launch_hinted<64, 2>(a, (uint32_t)cls[c].size(), D);
-                else if (c == 1) launch_hinted<128, 4>(a, (uint32_t)cls[c].size(), D);
-                else launch_hinted<400, 8>(a, (uint32_t)cls[c].size(), D);
-            }
-            HIP_CHECK(hipGetLastError());
-            stats().launches[2]++;
-            gather(false);
-            for (uint32_t rd : cls[c]) {
-                uint32_t e = 0;
-                for (uint64_t q = read_pair_off[rd]; q < read_pair_off[rd + 1]; q++) e |= rerr[q];
-                if (!e) continue;
-                if (e & SP_ERR_DUPLICATE) PHMM_THROW(PHMM_EINVAL, "duplicate node in a mapping list");
-                if ((e & (SP_ERR_LINKS | SP_ERR_CAPACITY)) && c < 2) cls[c + 1].push_back(rd);
-                else PHMM_THROW(PHMM_ECAPACITY, "mapping list needs more than 400 slots / 8 in-list parents");
-            }
-        }
-        gather(true);
-        trace("cnc: one-candidate classes");
-        // pairs that came back -inf: the wide-range pass of full_prob_reads_hinted (short lists first)
-        if (!knobs().no_exact_hinted) {
-            std::vector<size_t> xq;
-            for (size_t q = 0; q < pairs.size(); q++)
-                if (res[q] == -INFINITY) xq.push_back(q);
-            if (!xq.empty()) {
-                std::stable_partition(xq.begin(), xq.end(), [&](size_t q) { return mp->read_max_list[pairs[q].x] <= 64; });
-                size_t n_small = 0;
-                while (n_small < xq.size() && mp->read_max_list[pairs[xq[n_small]].x] <= 64) n_small++;
-                std::vector<uint2> xs(xq.size());  // {slot, read}
-                for (size_t i = 0; i < xq.size(); i++) xs[i] = make_uint2(pairs[xq[i]].y, pairs[xq[i]].x);
-                const size_t xres_at = (xs.size() * sizeof(uint2) + 255) / 256 * 256;
-                d_ids.reserve(xres_at + xs.size() * sizeof(double));
-                uint2 *dp = d_ids.as<uint2>();
-                double *dres = (double *)(d_ids.as<char>() + xres_at);
-                HIP_CHECK(hipMemcpyAsync(dp, xs.data(), xs.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
-                if (n_small)
-                    hipLaunchKernelGGL((hinted_exact_kernel<64, 256>), dim3((unsigned)n_small), dim3(64), 0, s, a,
-                                       (const uint2 *)dp, dres);
-                if (n_small < xs.size())
-                    hipLaunchKernelGGL((hinted_exact_kernel<PHMM_MAX_ACTIVE_NODES, 1024>), dim3((unsigned)(xs.size() - n_small)),
-                                       dim3(64), 0, s, a, (const uint2 *)(dp + n_small), dres + n_small);
-                if (job.on_device)
-                    hipLaunchKernelGGL(cnc_scatter, dim3((unsigned)((xs.size() + 255) / 256)), dim3(256), 0, s,
-                                       (const uint2 *)dp, (const double *)dres, xs.size(), R, d_out.as<double>());
-                HIP_CHECK(hipGetLastError());
-                std::vector<double> hres(xs.size());
-                HIP_CHECK(hipMemcpyAsync(hres.data(), dres, hres.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                for (size_t i = 0; i < xq.size(); i++)
-                    if (hres[i] == hres[i]) res[xq[i]] = hres[i];
-                stats().launches[2]++;
-            }
-        }
+        HIP_CHECK(hipMemcpyAsync(d_mask.p, pairs.data(), pairs.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+        HintedWork w;
+        w.planes = D;
+        w.call_cands = C;
+        w.pair_off = read_pair_off.data();
+        w.pairs = pairs.data();
+        w.d_pairs = d_mask.as<uint2>();
+        w.d_res = (double *)(d_mask.as<char>() + res_at);
+        w.d_rerr = (uint32_t *)(d_mask.as<char>() + rerr_at);
+        w.scatter_exact = job.on_device;
+        w.vals = res.data();
+        hinted_run(m, reads, mp,
+                   hinted_args(m, reads, mp, D, ws(m, WS_CAND_INIT).as<double>(), ws(m, WS_CAND_TRANS).as<double>(), nullptr), w);
     }
     stats().ms[2] += tm.stop();  // (on top of the base pass; cells stay those of the base pass)
-    trace("cnc: exact pass");
 }
 
 }  // namespace
@@ -1826,7 +1842,7 @@ __global__ void __launch_bounds__(256) lk_commit(const uint64_t *read_off, uint6
 
 namespace {
 
-// values and total of the handle's state (or of a scored batch) through lk_compose, into aux[14]: cand | tot | out
+// values and total of the handle's state (or of a scored batch) through lk_compose, into WS_LK_COMPOSE: cand | tot | out
 struct Composed {
     const double *tot, *out;
 };
@@ -1835,7 +1851,7 @@ Composed lk_run_compose(const phmm_likelihood *lk, const std::vector<LkCand> &ca
     hipStream_t s = current_stream();
     const uint64_t R = lk->reads->R;
     const size_t C = cand.size();
-    DevBuf &buf = lk->m->wset().aux[14];
+    DevBuf &buf = ws(lk->m, WS_LK_COMPOSE);
     const size_t tot_at = (C * sizeof(LkCand) + 255) / 256 * 256, out_at = tot_at + (C * sizeof(double) + 255) / 256 * 256;
     buf.reserve(out_at + (want_out ? C * R * sizeof(double) : 0));
     LkCand *d_cand = buf.as<LkCand>();
@@ -1845,7 +1861,7 @@ Composed lk_run_compose(const phmm_likelihood *lk, const std::vector<LkCand> &ca
     hipLaunchKernelGGL(lk_compose, dim3((unsigned)C), dim3(256), 0, s, (const LkCand *)d_cand,
                        lk->reads->d_off.as<uint64_t>(), R, (const double *)lk->d_val.as<double>(),
                        (const unsigned long long *)lk->d_tat.as<unsigned long long>(), rmask,
-                       (const double *)lk->m->wset().aux[11].as<double>(), d_o, d_tot);
+                       (const double *)ws(lk->m, WS_OUT).as<double>(), d_o, d_tot);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(s));  // (cand is the caller's)
     return Composed{d_tot, d_o};
@@ -1987,7 +2003,7 @@ void likelihood_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_no
         // (the bits phmm_likelihood_current returns afterwards: the same values reduced over the same tree)
         std::vector<uint3> apply(n_chg);
         for (uint64_t j = 0; j < n_chg; j++) apply[j] = make_uint3(0, chg_node[j], chg_cn[j]);
-        DevBuf &d_apply = lk->m->wset().aux[14];
+        DevBuf &d_apply = ws(lk->m, WS_LK_COMPOSE);
         d_apply.reserve(std::max<size_t>(apply.size() * sizeof(uint3), 512));  // (lk_run_compose's own need: no growth below)
         double total = 0.0;
         if (R) {
@@ -2002,7 +2018,7 @@ void likelihood_move(phmm_likelihood *lk, uint64_t n_chg, const uint32_t *chg_no
         if (n_resc)
             hipLaunchKernelGGL(lk_commit, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s,
                                lk->reads->d_off.as<uint64_t>(), R, job.d_rmask, (uint32_t)job.full[0],
-                               (const double *)lk->m->wset().aux[11].as<double>(), (unsigned long long)T_new,
+                               (const double *)ws(lk->m, WS_OUT).as<double>(), (unsigned long long)T_new,
                                lk->d_val.as<double>(), lk->d_tat.as<unsigned long long>());
         if (by_group)
             hipLaunchKernelGGL(cng_apply, dim3((unsigned)apply.size()), dim3(256), 0, s, (const uint3 *)d_apply.as<uint3>(),
