@@ -69,6 +69,7 @@ void refresh_knobs() {
     k.no_exact_dense = flag("PHMM_NO_EXACT_DENSE");
     k.no_wide_hinted = flag("PHMM_NO_WIDE_HINTED");
     k.wide_hinted = flag("PHMM_WIDE_HINTED") && !k.no_wide_hinted;
+    k.no_wide_list_bwd = flag("PHMM_NO_WIDE_LIST_BWD");
     k.wide_hinted_cpb = num("PHMM_WIDE_HINTED_CPB", 0);
     if (k.wide_hinted_cpb != 1 && k.wide_hinted_cpb != 2 && k.wide_hinted_cpb != 4) k.wide_hinted_cpb = 0;
     k.no_side_worker = flag("PHMM_NO_SIDE_WORKER");

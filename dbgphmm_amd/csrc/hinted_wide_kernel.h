@@ -20,6 +20,12 @@
 // hinted_exact_kernel, as for the other classes).  A duplicate node is SP_ERR_DUPLICATE, a list beyond the block
 // SP_ERR_CAPACITY; the host hands any flagged read but a duplicate to the generic kernel.
 //
+// STORE (forward_with_mapping with stored columns, forward.rs:51-75; one candidate per block): every position also
+// leaves a forward record in HintedArgs::pool, the layout hinted_lean_kernel writes and load_record<CAP> /
+// wb_load_record read -- {n, na = n, E, 0}, ids padded to an even count, m[n] i[n] d[n] in list order, values in the
+// column's own scale.  One thread allocates, the offset travels through LDS; a full pool is SP_ERR_POOL.  The
+// flavours without it hold none of this (the statements are discarded at compile time).
+//
 // Included by sparse.hip behind HintedArgs / HStep.
 #pragma once
 
@@ -61,13 +67,14 @@ template <int HASH> __device__ __forceinline__ int hw_find(const uint32_t *key, 
 // Reads x candidates: grid (reads of the class, ceil(n_cand / CPB)), candidates blockIdx.y * CPB + c.
 // PAIRS: a block takes a work unit {read, CPB candidate slots} of read_ids, 0xffffffff for an idle slot.  An idle
 // slot computes nothing and writes nothing.
-template <int BS, int CPB, bool PAIRS>
+template <int BS, int CPB, bool PAIRS, bool STORE = false>
 // (448 threads are 7 waves: at 4 waves per SIMD -- 128 VGPRs -- two such blocks share a CU, at 3 only one)
 __global__ void __launch_bounds__(BS, BS > 128 ? 4 : 1) hinted_wide_kernel(const HintedArgs a, const uint32_t n_cand) {
     constexpr int NW = BS / 64;
     using Sh = HintedWideShared<BS, CPB>;
     constexpr int HASH = Sh::HASH;
     static_assert(BS % 64 == 0 && NW <= 8, "block shape");
+    static_assert(!STORE || (CPB == 1 && !PAIRS), "a stored-column call is one candidate on the reads x candidates grid");
     __shared__ Sh sh;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const uint32_t *unit = a.read_ids + (size_t)blockIdx.x * (1 + CPB);
@@ -264,6 +271,34 @@ __global__ void __launch_bounds__(BS, BS > 128 ? 4 : 1) hinted_wide_kernel(const
             if (has) {
                 sh.G[c][t] = HStep::lin3(lp.p_MM, pm[c], lp.p_IM, pi[c], lp.p_DM, pd[c]);
                 sh.H[c][t] = HStep::lin3(lp.p_MI, pm[c], lp.p_II, pi[c], lp.p_DI, pd[c]);
+            }
+        }
+        if constexpr (STORE) {
+            // ---- forward record of the position (every entry carries m, i and d; slot t = entry t)
+            __shared__ unsigned long long rec_o;
+            const uint64_t idb = (uint64_t)((n + 1) & ~1) * 4;
+            const uint64_t bytes = 16 + idb + (uint64_t)(3 * n) * 8;
+            if (t == 0) rec_o = atomicAdd(a.pool.top, (unsigned long long)bytes);
+            hw_sync();
+            const uint64_t o = rec_o;
+            if (o + bytes > a.pool.cap) {  // (block-uniform: every thread read the same offset)
+                err |= SP_ERR_POOL;
+                break;
+            }
+            uint8_t *rec = a.pool.base + o;
+            if (t == 0) {
+                ((uint32_t *)rec)[0] = (uint32_t)n;
+                ((uint32_t *)rec)[1] = (uint32_t)n;
+                ((int *)rec)[2] = Eprev[0];
+                ((uint32_t *)rec)[3] = 0;
+                a.pool.off[b0 + pos] = o + 8;
+            }
+            if (has) {
+                ((uint32_t *)(rec + 16))[t] = id_cur;
+                double *om = (double *)(rec + 16 + idb);
+                om[t] = pm[0];
+                om[n + t] = pi[0];
+                om[2 * n + t] = pd[0];
             }
         }
         // ---- the column becomes the previous one

@@ -1129,7 +1129,7 @@ void mapping_backward_chunk(MapChunk &mc, const std::vector<uint32_t> &sparse_la
                 else if (kind == 0)
                     hipLaunchKernelGGL((sparse_backward_kernel<64>), dim3((unsigned)who.size()), dim3(64), 0, s, ba);
                 else if (wide_ok)  // the 400-slot class on a block of 448 threads (wide_bwd_kernel.h)
-                    hipLaunchKernelGGL(wide_backward_kernel, dim3((unsigned)who.size()), dim3(WBK_T), 0, s, ba);
+                    hipLaunchKernelGGL(wide_backward_kernel<false>, dim3((unsigned)who.size()), dim3(WBK_T), 0, s, ba);
                 else
                     hipLaunchKernelGGL((sparse_backward_kernel<KMAX>), dim3((unsigned)who.size()), dim3(64), 0, s, ba);
                 HIP_CHECK(hipGetLastError());
@@ -1691,8 +1691,11 @@ void mappings_map_nodes(phmm_model *m, const phmm_reads *reads, const phmm_mappi
 // forward_with_mapping (forward.rs:51-75) of every read with one record per position, into the workspace pool `fp`,
 // and the arguments of the list pass that walks back over those records (sparse_backward_kernel, list mode): per-read
 // ln P in lf, the reads split into the 64- and 400-slot classes.  The caller sets what the pass emits.
+// With PHMM_WIDE_HINTED the forward half of reads with lists of 65-400 nodes runs on a block (hinted_wide_kernel.h,
+// its record-storing flavour).  d_cells: a zeroed device counter for the statistics of a block backward.
 static void hinted_list_pass_setup(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in,
-                                   std::vector<double> &lf, SparseBwdArgs &ba, std::vector<uint32_t> (&cls)[2]) {
+                                   std::vector<double> &lf, SparseBwdArgs &ba, std::vector<uint32_t> (&cls)[2],
+                                   unsigned long long **d_cells = nullptr) {
     hipStream_t s = current_stream();
     const uint64_t R = reads->R, n_pos = reads->total;
     upload_reads(reads);
@@ -1700,7 +1703,8 @@ static void hinted_list_pass_setup(phmm_model *m, const phmm_reads *reads, const
     // forward_with_mapping with one record per position
     DevBuf &fpool = m->wset().aux[1], &fmeta = m->wset().aux[2];
     RecPool fp{};
-    fp.cap = (n_pos * 24 + mp_in->total_entries * 28) * 3 + (1u << 20);  // a read may be redone in up to 3 capacity classes
+    // a read may be redone in up to 3 generic capacity classes -- with the block class on, behind one attempt there
+    fp.cap = (n_pos * 24 + mp_in->total_entries * 28) * (knobs().wide_hinted ? 4 : 3) + (1u << 20);
     fpool.reserve(fp.cap);
     fmeta.reserve(sizeof(unsigned long long) + sizeof(uint64_t) * (n_pos + 1));
     HIP_CHECK(hipMemsetAsync(fmeta.p, 0, sizeof(unsigned long long) + sizeof(uint64_t) * (n_pos + 1), s));
@@ -1723,7 +1727,8 @@ static void hinted_list_pass_setup(phmm_model *m, const phmm_reads *reads, const
     };
     const size_t o_len = carve(sizeof(int) * R), o_sw = carve(sizeof(int) * R), o_stop = carve(sizeof(int) * R),
                  o_err = carve(sizeof(uint32_t) * R), o_lanes = carve(sizeof(uint32_t) * R), o_logp = carve(sizeof(double) * R),
-                 o_logb = carve(sizeof(double) * R), o_bases = carve((size_t)R * Lb), o_hand = carve(sizeof(BHandoff));
+                 o_logb = carve(sizeof(double) * R), o_cells = carve(sizeof(unsigned long long)),
+                 o_bases = carve((size_t)R * Lb), o_hand = carve(sizeof(BHandoff));
     ctl.reserve(cb);
     char *cp = (char *)ctl.p;
     HIP_CHECK(hipMemsetAsync(cp, 0, o_bases, s));
@@ -1757,6 +1762,7 @@ static void hinted_list_pass_setup(phmm_model *m, const phmm_reads *reads, const
     ba.stop = (int *)(cp + o_stop);
     ba.hand = (BHandoff *)(cp + o_hand);
     ba.logb = (double *)(cp + o_logb);
+    if (d_cells) *d_cells = (unsigned long long *)(cp + o_cells);
     cls[0].clear();
     cls[1].clear();
     for (uint64_t r = 0; r < R; r++) cls[mp_in->read_max_list[r] <= 64 ? 0 : 1].push_back((uint32_t)r);
@@ -1783,13 +1789,50 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
     std::vector<double> lf;
     SparseBwdArgs ba{};
     std::vector<uint32_t> cls[2];
-    hinted_list_pass_setup(m, reads, mp_in, lf, ba, cls);
+    unsigned long long *d_cells = nullptr;
+    hinted_list_pass_setup(m, reads, mp_in, lf, ba, cls, &d_cells);
     // the pass emits the mapping lists (emit probs of every position)
     ba.ratio_lin = std::exp(-m->params.active_node_max_ratio);
     ba.topk = use_max_ratio ? 0 : (int)m->params.n_active_nodes;
     uint32_t *const d_lanes = const_cast<uint32_t *>(ba.lanes);
+    // lists of 65-400 nodes on a block (wide_backward_kernel<true>, wide_bwd_kernel.h): score-ratio lists over the packed
+    // adjacency records only, and opt-in with the forward's block class.  PHMM_NO_WIDE_LIST_BWD holds this half alone to
+    // the generic kernel
+    std::vector<uint32_t> wb;
+    if (knobs().wide_hinted && use_max_ratio && m->dev.max_degree <= (uint32_t)ADJ_DEG && !knobs().no_wide_list_bwd) {
+        std::vector<uint32_t> rest;
+        for (uint32_t r : cls[1]) (mp_in->read_max_list[r] <= (uint32_t)WBK_CAP ? wb : rest).push_back(r);
+        cls[1].swap(rest);
+    }
+    CallStats &st = stats();
     for (int attempt = 0;; attempt++) {
         ba.mpool = sink.mp;
+        if (!wb.empty()) {
+            WideBwdListArgs wa{};
+            static_cast<SparseBwdArgs &>(wa) = ba;
+            wa.cells = d_cells;
+            LaunchTimer lt(timing_enabled());
+            HIP_CHECK(hipMemcpyAsync(d_lanes, wb.data(), sizeof(uint32_t) * wb.size(), hipMemcpyHostToDevice, s));
+            lt.begin();
+            hipLaunchKernelGGL(wide_backward_kernel<true>, dim3((unsigned)wb.size()), dim3(WBK_T), 0, s, wa);
+            lt.end();
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipStreamSynchronize(s));  // the lane list is reused by the next class
+            st.launches[4]++;
+            st.ms[4] += lt.total_ms();
+            // a read the block flags with anything but a full pool (the retry below redoes every read) goes to the generic
+            // kernel, which reports what it finds
+            std::vector<uint32_t> herr(R), redo;
+            HIP_CHECK(hipMemcpy(herr.data(), ba.err, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+            for (uint32_t r : wb)
+                if (herr[r] && !(herr[r] & SP_ERR_POOL)) redo.push_back(r);
+            if (!redo.empty()) {
+                HIP_CHECK(hipMemcpyAsync(d_lanes, redo.data(), sizeof(uint32_t) * redo.size(), hipMemcpyHostToDevice, s));
+                hipLaunchKernelGGL((sparse_backward_kernel<KMAX>), dim3((unsigned)redo.size()), dim3(64), 0, s, ba);
+                HIP_CHECK(hipGetLastError());
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
         for (int c = 0; c < 2; c++) {
             if (cls[c].empty()) continue;
             HIP_CHECK(hipMemcpyAsync(d_lanes, cls[c].data(), sizeof(uint32_t) * cls[c].size(), hipMemcpyHostToDevice, s));
@@ -1813,6 +1856,11 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
         HIP_CHECK(hipMemcpy(sink.mp.top, &zero, sizeof(zero), hipMemcpyHostToDevice));
         sink.mp.base = m->wset().aux[5].as<uint8_t>();
         sink.mp.cap = sink.cap;
+    }
+    if (!wb.empty()) {
+        unsigned long long h_cells = 0;
+        HIP_CHECK(hipMemcpy(&h_cells, d_cells, sizeof(h_cells), hipMemcpyDeviceToHost));
+        st.cells[4] += h_cells;
     }
     // backward_with_mapping's totals, ln B.tables[0].mb (the list kernels' last step)
     std::vector<double> lb(R);

@@ -418,8 +418,10 @@ struct Knobs {
     bool no_exact_dense = false;     // PHMM_NO_EXACT_DENSE: no log-domain pass over reads the dense certificate flags; their
                                      // scores come back NaN and their posteriors are left out (phmm_dense_tables ignores it)
     bool wide_hinted = false;        // PHMM_WIDE_HINTED (and PHMM_NO_WIDE_HINTED unset): mapping lists of 65-400 nodes on a block
-                                     // (hinted_wide_kernel.h).  Opt-in until it is timed against the generic kernels
+                                     // (hinted_wide_kernel.h; the list pass: also wide_bwd_kernel.h).  Opt-in: DESIGN.md section 6
     bool no_wide_hinted = false;     // PHMM_NO_WIDE_HINTED: generic kernels for mapping lists of 65-400 nodes (hinted forward)
+    bool no_wide_list_bwd = false;   // PHMM_NO_WIDE_LIST_BWD: with PHMM_WIDE_HINTED, the list backward of generate_mappings on carried
+                                     // lists stays on the generic kernel (wide_bwd_kernel.h) -- the two halves apart, for tests
     int wide_hinted_cpb = 0;         // PHMM_WIDE_HINTED_CPB: candidates per block of that class, 1 / 2 / 4 (anything else, 0: automatic)
     bool no_side_worker = false;     // PHMM_NO_SIDE_WORKER
     bool no_wide_handover = false;   // PHMM_NO_WIDE_HANDOVER

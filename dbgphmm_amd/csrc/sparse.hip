@@ -993,7 +993,12 @@ inline int hinted_wide_cpb(int wc, uint64_t n_reads, uint64_t n_pairs) {
 }
 template <bool PAIRS> void launch_hinted_wide(int wc, int cpb, const HintedArgs &a, dim3 grid, uint32_t n_cand) {
     hipStream_t s = current_stream();
-    if (wc == 0) {
+    if (a.pool.base) {
+        // stored columns (forward_with_mapping): one candidate, one block per read, a record per position
+        if constexpr (PAIRS) PHMM_THROW(PHMM_EINTERNAL, "hinted wide class: stored columns on work units");
+        else if (wc == 0) hipLaunchKernelGGL((hinted_wide_kernel<128, 1, false, true>), grid, dim3(128), 0, s, a, n_cand);
+        else hipLaunchKernelGGL((hinted_wide_kernel<448, 1, false, true>), grid, dim3(448), 0, s, a, n_cand);
+    } else if (wc == 0) {
         if (cpb >= 4) hipLaunchKernelGGL((hinted_wide_kernel<128, 4, PAIRS>), grid, dim3(128), 0, s, a, n_cand);
         else if (cpb == 2) hipLaunchKernelGGL((hinted_wide_kernel<128, 2, PAIRS>), grid, dim3(128), 0, s, a, n_cand);
         else hipLaunchKernelGGL((hinted_wide_kernel<128, 1, PAIRS>), grid, dim3(128), 0, s, a, n_cand);
@@ -1424,8 +1429,11 @@ void hinted_run(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp,
     const bool packed_ok = w.call_cands >= 2 && !w.pool && lean_ok && !knobs().no_packed;
     // lists of 65-400 nodes: one block per read (hinted_wide_kernel.h).  By the read's lists, the model and the knobs
     // only -- never by the candidate count: a batch stays bit-equal to one-candidate calls.  The class is opt-in
-    // (PHMM_WIDE_HINTED): it has not been timed against the generic kernels, and speed is its only purpose
-    const bool wide_ok = lean_ok && !w.pool && knobs().wide_hinted;
+    // (PHMM_WIDE_HINTED): speed is its only purpose, and the timings so far do not make it the
+    // default.  A call that stores the columns (w.pool: forward_with_mapping) takes the record-storing flavour; a read
+    // the class flags is redone by the generic class, whose records replace the block's (pool.off[] points at the later
+    // record, the earlier bytes stay unused)
+    const bool wide_ok = lean_ok && knobs().wide_hinted;
     std::vector<uint32_t> cls[3], pcls[3], wcls[2];
     for (uint64_t r = 0; r < R; r++) {
         if (w.pair_off[r + 1] == w.pair_off[r]) continue;
@@ -1475,7 +1483,8 @@ void hinted_run(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp,
         words.clear();
         int cpb[2];
         for (int wc = 0; wc < 2; wc++) {
-            cpb[wc] = hinted_wide_cpb(wc, wcls[wc].size(), class_pairs(wcls[wc]));
+            // (a stored-column call is one candidate: one per block whatever the knob says)
+            cpb[wc] = w.pool ? 1 : hinted_wide_cpb(wc, wcls[wc].size(), class_pairs(wcls[wc]));
             L[wc] = hinted_list(w, wcls[wc], (unsigned)cpb[wc], false, words);
         }
         const size_t cells_at = (words.size() * sizeof(uint32_t) + 7) / 8 * 8;

@@ -8,7 +8,20 @@
 // over the slots: seven iterations of a wave on a 400-node column, one here.  Same statements, same per-node summation
 // order (the packed records keep the CSR order of a node's children); a slot's adjacency record and the slots of its
 // in-list children are found once per position and stay in the thread's registers through the Del sweeps.
-// Score-ratio lists only (topk == 0), no list mode, packed records: the host keeps the generic kernel otherwise.
+// Score-ratio lists only (topk == 0), packed records: the host keeps the generic kernel otherwise.
+//
+// Two flavours behind a template flag, as the EDGES flag of sparse_backward_kernel (what belongs to the other flavour is
+// discarded at compile time: the adaptive flavour's instructions are those it had before the flag):
+//   * wide_backward_kernel<false>: backward_by_forward of the adaptive flow -- the node list of a column is the forward
+//     record's elements by total, bursts and hand-offs between the capacity classes, the dense hand-over at s0;
+//   * wide_backward_kernel<true>: backward_with_mapping (backward.rs:59-93, the list mode of sparse_backward_kernel,
+//     mapping_flow.hip) -- the node list of position pos is mapping.nodes(pos), read from a.list_nodes into sh.list in
+//     the place of the sort.  The walk goes down to position 0, whose column has no forward record and emits nothing:
+//     only its MatchBegin, summed over the list at that position alone, leaves the kernel as a.logb (the read's
+//     backward total).  No hand-off, no burst, no dense hand-over; a.stop / a.err as the one-wave list kernel leaves
+//     them (a missing forward record or a list beyond the block: SP_ERR_CAPACITY).
+// Every exit from the walk is taken by the whole block: it is decided from values every thread holds alike (a record
+// offset or a list size read from memory, an allocation published through LDS).
 #pragma once
 
 #include "block_sort.h"
@@ -175,7 +188,15 @@ __device__ __forceinline__ bool wb_emit(const RecPool &mp, uint64_t pos_index, W
     return true;
 }
 
-__global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArgs a) {
+// The list flavour's arguments: a.cells is the call statistics' counter, list entries of the columns computed.
+struct WideBwdListArgs : SparseBwdArgs {
+    unsigned long long *cells;
+};
+template <bool LIST> using WideBwdArgsOf = typename std::conditional<LIST, WideBwdListArgs, SparseBwdArgs>::type;
+
+// (LIST: 4 waves per SIMD -- 128 VGPRs -- let two blocks share a CU, as the adaptive flavour's 127 do unasked)
+template <bool LIST = false>
+__global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(const WideBwdArgsOf<LIST> a) {
     __shared__ WideBwdShared sh;
     const int t = threadIdx.x;
     const uint32_t gi = a.lanes[blockIdx.x];
@@ -196,7 +217,12 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
     bool stopped = false;
     int stop_at = 0;
     int fn = 0, fna = 0, fE = 0;
-    if (a.mode == 0) {
+    // (LIST) MatchBegin and exponent of column 0 once it is computed, entries of the columns computed so far
+    double mb0 = 0.0;
+    int E0 = 0;
+    bool done0 = false;
+    unsigned long long n_cells = 0;
+    if (LIST || a.mode == 0) {
         pos = len - 1;
         // merged index len: F.tables[len-1] (.) b_init / P   (table.rs:414-434, backward.rs:197-211)
         if (!wb_load_record(a.fpool, p0 + (uint64_t)(len - 1), sh, fn, fna, fE)) {
@@ -234,26 +260,39 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
         }
     }
     int steps_done = 0;
-    for (; !stopped && pos >= s0 + 1 && !err; pos--) {
+    // (LIST) the walk goes on to position 0: B.tables[0] over mapping.nodes(0), begin states only
+    for (; !stopped && pos >= (LIST ? 0 : s0 + 1) && !err; pos--) {
         // B.tables[pos] over filled_nodes(F.tables[pos-1]) (backward.rs:122-129)
-        if (!wb_load_record(a.fpool, p0 + (uint64_t)(pos - 1), sh, fn, fna, fE)) {
+        if ((!LIST || pos > 0) && !wb_load_record(a.fpool, p0 + (uint64_t)(pos - 1), sh, fn, fna, fE)) {
             stopped = true;
             stop_at = pos;
             break;
         }
         double *val = sh.dA;
-        uint16_t *order = (uint16_t *)sh.dB;
-        // filled_nodes (table.rs:117-123): the record's elements by total, stable (sort_desc, frontier_dev.h)
-        {
-            const int NP = bitonic_size(fn);
-            for (int k = t; k < NP; k += WBK_T) {
-                val[k] = k < fn ? sh.fm[k] + sh.fi[k] + sh.fd[k] : -1.0;
-                order[k] = (uint16_t)k;
+        int nl;
+        if constexpr (LIST) {
+            // mapping.nodes(pos) (backward.rs:59-90)
+            const uint64_t l0 = a.list_off[q0 + (uint64_t)pos];
+            nl = (int)(a.list_off[q0 + (uint64_t)pos + 1] - l0);
+            if (nl > WBK_CAP) {  // (the same for every thread)
+                err |= SP_ERR_CAPACITY;
+                break;
             }
-            block_bitonic_desc(val, order, NP);
+            if (t < nl) sh.list[t] = a.list_nodes[l0 + t];
+        } else {
+            uint16_t *order = (uint16_t *)sh.dB;
+            // filled_nodes (table.rs:117-123): the record's elements by total, stable (sort_desc, frontier_dev.h)
+            {
+                const int NP = bitonic_size(fn);
+                for (int k = t; k < NP; k += WBK_T) {
+                    val[k] = k < fn ? sh.fm[k] + sh.fi[k] + sh.fd[k] : -1.0;
+                    order[k] = (uint16_t)k;
+                }
+                block_bitonic_desc(val, order, NP);
+            }
+            nl = fna < fn ? fna : fn;
+            if (t < nl) sh.list[t] = sh.fid[order[t]];
         }
-        const int nl = fna < fn ? fna : fn;
-        if (t < nl) sh.list[t] = sh.fid[order[t]];
         __syncthreads();
         // ---- one backward column over the list (bwd_list_step, sparse_dev.h)
         const WBCol &prev = sh.col[(pos + 1) & 1];
@@ -306,6 +345,9 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
             // bib (backward.rs:535-555), the m' half of this node's term: the node's own m'[v] sits in the slot the Ins term
             // just found; the d half is added at the rescale
             sh.bterm[t] = lp.p_IM * rec.init * (rec.emis == x ? lp.p_match : lp.p_mismatch) * mv;
+            // (LIST) bmb (backward.rs:499-519) is wanted of column 0 alone: the same sum with p_MM / p_MD, in sh.fm --
+            // position 0 has no forward record
+            if (LIST && pos == 0) sh.fm[t] = lp.p_MM * rec.init * (rec.emis == x ? lp.p_match : lp.p_mismatch) * mv;
             const double d0 = lp.p_DM * a1 + lp.p_DI * qq;
             cur.d[t] = d0;
             sh.dA[t] = d0;
@@ -349,6 +391,7 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
             cur.i[t] = ni * sc;
             cur.d[t] = nd * sc;
             sh.bterm[t] = (sh.bterm[t] + lp.p_ID * rec.init * nd) * sc;
+            if (LIST && pos == 0) sh.fm[t] = (sh.fm[t] + lp.p_MD * rec.init * nd) * sc;
         }
         if (t == 0) cur.E = Ecur;
         __syncthreads();
@@ -364,6 +407,23 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
             }
             const double ib = wave_sum(part) + lp.p_II * lp.p_random * (prev_is_init ? 0.0 : sh.ib[(pos + 1) & 1]) * sc;
             if (t == 0) sh.ib[pos & 1] = ib;
+            if (LIST && pos == 0) {
+                double pm = 0.0;
+#pragma unroll 1
+                for (int w = 0; w < WBK_WAVES; w++) {
+                    const int k = t + 64 * w;
+                    if (k < nl) pm += sh.fm[k];
+                }
+                mb0 = wave_sum(pm) + lp.p_MI * lp.p_random * (prev_is_init ? 0.0 : sh.ib[(pos + 1) & 1]) * sc;
+            }
+        }
+        if constexpr (LIST) {
+            n_cells += (unsigned long long)nl;
+            if (pos == 0) {  // column 0 has no F.tables[-1]: nothing to emit
+                E0 = Ecur;
+                done0 = true;
+                break;
+            }
         }
         // S = F.tables[pos-1] (.) B.tables[pos] / P over F's elements (table.rs:320-345, 500-505)
         const double w = ok ? exp((double)(fE + Ecur) * SP_LN2 - logP) : 0.0;
@@ -374,13 +434,21 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
         __syncthreads();
         if (!wb_emit(a.mpool, q0 + (uint64_t)(pos - 1), sh, par, fn, a.ratio_lin)) err |= SP_ERR_POOL;
         // a burst (max_steps) ends where the column fits the one-lane-per-node class again
-        if (a.max_steps > 0 && !err && ++steps_done >= a.max_steps && nl <= 64 && pos - 1 >= s0 + 1) {
+        if (!LIST && a.max_steps > 0 && !err && ++steps_done >= a.max_steps && nl <= 64 && pos - 1 >= s0 + 1) {
             stopped = true;
             stop_at = pos - 1;
             break;
         }
     }
-    if (stopped && !err) {
+    if constexpr (LIST) {
+        if (stopped) err |= SP_ERR_CAPACITY;  // a forward record is missing or larger than the block
+        if (t == 0) {
+            a.stop[gi] = stopped ? stop_at : s0;
+            // ln B.tables[0].mb
+            if (a.logb && done0 && !err) a.logb[gi] = log(mb0) + (double)E0 * SP_LN2;
+            if (a.cells && n_cells) atomicAdd(a.cells, n_cells);
+        }
+    } else if (stopped && !err) {
         // park B.tables[stop_at + 1] for the next phase
         if (have_cols && stop_at < len) {
             const WBCol &c = sh.col[(stop_at + 1) & 1];
@@ -429,5 +497,6 @@ __global__ void __launch_bounds__(WBK_T) wide_backward_kernel(const SparseBwdArg
     }
     if (t == 0) a.err[gi] = err;
 }
+
 
 }  // namespace phmm

@@ -381,7 +381,13 @@ int phmm_run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const ph
  * 65-400 nodes, one block per read and candidate group; its launches and time are part
  * of class 2 as well; cells = list entries x candidates it scored; all 0 when the call
  * had no such read or the class is off: it is opt-in, PHMM_WIDE_HINTED=1, and
- * PHMM_NO_WIDE_HINTED=1 wins over that).  Any other index is PHMM_EINVAL. */
+ * PHMM_NO_WIDE_HINTED=1 wins over that).  Index 4 also covers the list pass: the wide
+ * classes on mapping lists.  In phmm_generate_mappings with mappings and in
+ * phmm_run_with_mapping_edges it counts the record-storing forward on a block (cells =
+ * list entries of its reads) and, for phmm_generate_mappings with use_max_ratio, the
+ * list backward on a block (one launch; cells = list entries of the positions it
+ * computed).  The developer knob PHMM_NO_WIDE_LIST_BWD=1 keeps that backward on the
+ * generic kernel while the forward stays on the block.  Any other index is PHMM_EINVAL. */
 int phmm_last_call_stats(int which, double *out_ms, uint64_t *out_launches,
                          uint64_t *out_cells);
 int phmm_enable_timing(int on);
