@@ -70,6 +70,9 @@ void refresh_knobs() {
     k.no_wide_hinted = flag("PHMM_NO_WIDE_HINTED");
     k.wide_hinted = flag("PHMM_WIDE_HINTED") && !k.no_wide_hinted;
     k.no_wide_list_bwd = flag("PHMM_NO_WIDE_LIST_BWD");
+    k.wide_edge_bwd = flag("PHMM_WIDE_EDGE_BWD");
+    k.wide_bwd_t = num("PHMM_WIDE_BWD_T", 0);
+    if (k.wide_bwd_t != 128 && k.wide_bwd_t != 448) k.wide_bwd_t = 0;
     k.wide_hinted_cpb = num("PHMM_WIDE_HINTED_CPB", 0);
     if (k.wide_hinted_cpb != 1 && k.wide_hinted_cpb != 2 && k.wide_hinted_cpb != 4) k.wide_hinted_cpb = 0;
     k.no_side_worker = flag("PHMM_NO_SIDE_WORKER");

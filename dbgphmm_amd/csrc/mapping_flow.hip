@@ -1768,6 +1768,45 @@ static void hinted_list_pass_setup(phmm_model *m, const phmm_reads *reads, const
     for (uint64_t r = 0; r < R; r++) cls[mp_in->read_max_list[r] <= 64 ? 0 : 1].push_back((uint32_t)r);
 }
 
+// The list backward on a block (wide_bwd_kernel.h) for the reads `wb`, one launch per block size: the reads whose longest
+// list holds at most 128 nodes may take the 128-thread block, the rest the 448-thread one (the same bits either way).
+// PHMM_WIDE_BWD_T=128 / 448 decides for the former.  Automatic: the small block when there are more such reads than
+// 448-thread blocks the device holds at once (two per CU, 64 KB of LDS each) -- then the launch is bound by how many
+// blocks run side by side, and seven small ones fit a CU; with fewer, a launch lasts as long as its longest read and a
+// second launch only adds its own (slower at 26 and 60 such reads, faster at 3007).
+// Index 4 of the statistics counts the launches.
+template <bool EDGES>
+static void launch_wide_list_backward(const phmm_mappings *mp_in, const std::vector<uint32_t> &wb, uint32_t *d_lanes,
+                                      const WideBwdArgsOf<true, EDGES> &wa) {
+    hipStream_t s = current_stream();
+    CallStats &st = stats();
+    size_t n_small = 0;
+    for (uint32_t r : wb) n_small += mp_in->read_max_list[r] <= (uint32_t)WBK_T_SMALL ? 1 : 0;
+    bool use_small = knobs().wide_bwd_t == WBK_T_SMALL;
+    if (knobs().wide_bwd_t == 0 && n_small) {
+        int dev = 0, cus = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        use_small = n_small > (size_t)2 * (size_t)cus;
+    }
+    std::vector<uint32_t> by_size[2];  // 448, 128
+    for (uint32_t r : wb) by_size[use_small && mp_in->read_max_list[r] <= (uint32_t)WBK_T_SMALL ? 1 : 0].push_back(r);
+    for (int c = 0; c < 2; c++) {
+        const std::vector<uint32_t> &who = by_size[c];
+        if (who.empty()) continue;
+        LaunchTimer lt(timing_enabled());
+        HIP_CHECK(hipMemcpyAsync(d_lanes, who.data(), sizeof(uint32_t) * who.size(), hipMemcpyHostToDevice, s));
+        lt.begin();
+        if (c == 0) hipLaunchKernelGGL((wide_backward_kernel<true, EDGES, WBK_T>), dim3((unsigned)who.size()), dim3(WBK_T), 0, s, wa);
+        else hipLaunchKernelGGL((wide_backward_kernel<true, EDGES, WBK_T_SMALL>), dim3((unsigned)who.size()), dim3(WBK_T_SMALL), 0, s, wa);
+        lt.end();
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));  // the lane list is reused by the next launch
+        st.launches[4]++;
+        st.ms[4] += lt.total_ms();
+    }
+}
+
 // PHMMModel::generate_mappings(reads, Some(mappings), use_max_ratio): run_with_mapping
 // (freq.rs:72-76) = forward_with_mapping (forward.rs:51-75) + backward_with_mapping
 // (backward.rs:59-93), then to_mapping_by_score_ratio / to_mapping(n_active) (hint.rs:124-142).
@@ -1811,15 +1850,7 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
             WideBwdListArgs wa{};
             static_cast<SparseBwdArgs &>(wa) = ba;
             wa.cells = d_cells;
-            LaunchTimer lt(timing_enabled());
-            HIP_CHECK(hipMemcpyAsync(d_lanes, wb.data(), sizeof(uint32_t) * wb.size(), hipMemcpyHostToDevice, s));
-            lt.begin();
-            hipLaunchKernelGGL(wide_backward_kernel<true>, dim3((unsigned)wb.size()), dim3(WBK_T), 0, s, wa);
-            lt.end();
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(s));  // the lane list is reused by the next class
-            st.launches[4]++;
-            st.ms[4] += lt.total_ms();
+            launch_wide_list_backward<false>(mp_in, wb, d_lanes, wa);
             // a read the block flags with anything but a full pool (the retry below redoes every read) goes to the generic
             // kernel, which reports what it finds
             std::vector<uint32_t> herr(R), redo;
@@ -1940,7 +1971,8 @@ void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_m
     std::vector<double> lf;
     SparseBwdEdgeArgs ba{};
     std::vector<uint32_t> cls[2];
-    hinted_list_pass_setup(m, reads, mp_in, lf, ba, cls);
+    unsigned long long *d_cells = nullptr;
+    hinted_list_pass_setup(m, reads, mp_in, lf, ba, cls, &d_cells);
     ba.logb = nullptr;
     ba.E = E;
     // record bounds -> slot offsets
@@ -1969,6 +2001,27 @@ void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_m
     ba.rec_val = d_val.as<double>();
     ba.rec_cnt = rec_cnt;
     uint32_t *const d_lanes = const_cast<uint32_t *>(ba.lanes);
+    // lists of 65-400 nodes on a block (wide_backward_kernel<true, true>, wide_bwd_kernel.h): packed adjacency records only,
+    // and opt-in beside the forward's block class (PHMM_WIDE_EDGE_BWD).  A read the block flags is rerun by the generic
+    // kernel, which rewrites the read's records and counts from their fixed slots and reports what it finds
+    if (knobs().wide_hinted && knobs().wide_edge_bwd && !knobs().no_wide_list_bwd && m->dev.max_degree <= (uint32_t)ADJ_DEG) {
+        std::vector<uint32_t> wb, rest;
+        for (uint32_t r : cls[1]) (mp_in->read_max_list[r] <= (uint32_t)WBK_CAP ? wb : rest).push_back(r);
+        if (!wb.empty()) {
+            WideBwdEdgeArgs wa{};
+            static_cast<SparseBwdEdgeArgs &>(wa) = ba;
+            wa.cells = d_cells;
+            launch_wide_list_backward<true>(mp_in, wb, d_lanes, wa);
+            unsigned long long h_cells = 0;
+            HIP_CHECK(hipMemcpy(&h_cells, d_cells, sizeof(h_cells), hipMemcpyDeviceToHost));
+            stats().cells[4] += h_cells;
+            std::vector<uint32_t> herr(R);
+            HIP_CHECK(hipMemcpy(herr.data(), ba.err, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+            for (uint32_t r : wb)
+                if (herr[r]) rest.push_back(r);
+        }
+        cls[1].swap(rest);
+    }
     for (int c = 0; c < 2; c++) {
         if (cls[c].empty()) continue;
         HIP_CHECK(hipMemcpyAsync(d_lanes, cls[c].data(), sizeof(uint32_t) * cls[c].size(), hipMemcpyHostToDevice, s));

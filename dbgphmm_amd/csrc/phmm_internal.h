@@ -422,6 +422,11 @@ struct Knobs {
     bool no_wide_hinted = false;     // PHMM_NO_WIDE_HINTED: generic kernels for mapping lists of 65-400 nodes (hinted forward)
     bool no_wide_list_bwd = false;   // PHMM_NO_WIDE_LIST_BWD: with PHMM_WIDE_HINTED, the list backward of generate_mappings on carried
                                      // lists stays on the generic kernel (wide_bwd_kernel.h) -- the two halves apart, for tests
+    bool wide_edge_bwd = false;      // PHMM_WIDE_EDGE_BWD: with PHMM_WIDE_HINTED, the backward half of run_with_mapping_edges on a block
+                                     // as well (wide_backward_kernel<true, true>).  Opt-in of its own: DESIGN.md section 6
+    int wide_bwd_t = 0;              // PHMM_WIDE_BWD_T: threads of the list backward's block for reads with lists of at most 128 nodes,
+                                     // 128 / 448 (anything else, 0: automatic -- 128 when there are more such reads than 448-thread
+                                     // blocks the device holds at once, mapping_flow.hip)
     int wide_hinted_cpb = 0;         // PHMM_WIDE_HINTED_CPB: candidates per block of that class, 1 / 2 / 4 (anything else, 0: automatic)
     bool no_side_worker = false;     // PHMM_NO_SIDE_WORKER
     bool no_wide_handover = false;   // PHMM_NO_WIDE_HANDOVER

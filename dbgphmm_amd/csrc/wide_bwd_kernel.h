@@ -20,6 +20,15 @@
 //     only its MatchBegin, summed over the list at that position alone, leaves the kernel as a.logb (the read's
 //     backward total).  No hand-off, no burst, no dense hand-over; a.stop / a.err as the one-wave list kernel leaves
 //     them (a missing forward record or a list beyond the block: SP_ERR_CAPACITY).
+//   * wide_backward_kernel<true, true>: the transition-posterior form of the list flavour (sparse_backward_kernel<CAP,
+//     true>, mapping_flow.hip): the same columns, and where the list flavour cuts the posterior into a mapping list this
+//     one writes the edge and Begin terms of merged index pos (emit_edge_terms / emit_begin_terms, thread = slot) into
+//     the record of position pos.  A thread's terms go behind those of the threads before it (a block scan of the
+//     counts of non-zero terms): slot-major, child-minor, the order rec_append gives the one-wave kernel's chunks of 64.
+// The block has two sizes (BS): 448 threads for lists of up to 400 nodes, and, for the list flavours, 128 threads (two
+// waves, a third of the LDS) for reads whose longest list holds at most 128 nodes.  Both run the same per-slot
+// expressions, the same wave-0 sums (lane j adds the slots j, j + 64, ...), the same sorting network on the same padded
+// size and the same scan offsets: the small block gives the bits of the large one.
 // Every exit from the walk is taken by the whole block: it is decided from values every thread holds alike (a record
 // offset or a list size read from memory, an allocation published through LDS).
 #pragma once
@@ -30,35 +39,39 @@
 namespace phmm {
 
 static constexpr int WBK_T = 448;
-static constexpr int WBK_WAVES = WBK_T / 64;
+static constexpr int WBK_T_SMALL = 128;  // the list flavours' block for reads with lists of at most 128 nodes
 static constexpr int WBK_CAP = PHMM_MAX_ACTIVE_NODES;
-static constexpr int WBK_HASH = 1024;
 
-struct WBCol {
-    double m[WBK_T], i[WBK_T], d[WBK_T];
-    uint32_t id[WBK_T];
-    uint32_t hkey[WBK_HASH];
-    uint16_t hslot[WBK_HASH];
+template <int BS> struct WBColT {
+    static constexpr int HASH = BS > 128 ? 1024 : 512, HASH_SHIFT = BS > 128 ? 22 : 23;
+    double m[BS], i[BS], d[BS];
+    uint32_t id[BS];
+    uint32_t hkey[HASH];
+    uint16_t hslot[HASH];
     int n, E;
 };
-struct WideBwdShared {
-    WBCol col[2];
-    double fm[WBK_T], fi[WBK_T], fd[WBK_T];  // the forward record
-    uint32_t fid[WBK_T];
-    double dA[512], dB[512];      // level buffers; outside the column step: val = dA, order = dB, the list entries being
+template <int BS> struct WideBwdSharedT {
+    static constexpr int T = BS, WAVES = BS / 64, CAP = BS < WBK_CAP ? BS : WBK_CAP, LEVEL = BS > 128 ? 512 : 128;
+    WBColT<BS> col[2];
+    double fm[BS], fi[BS], fd[BS];  // the forward record
+    uint32_t fid[BS];
+    double dA[LEVEL], dB[LEVEL];  // level buffers; outside the column step: val = dA, order = dB, the list entries being
                                   // sorted = (dB, list)
-    uint32_t list[512];
+    uint32_t list[LEVEL];
     double red[2][8];
     int wsum[2][8];
-    double bterm[WBK_T];  // per slot: its term of bib's sum over the list, init_v (p_IM e_v(x) m'[v] + p_ID d[v])
-    double ib[2];         // InsBegin of B.tables[p], in its column's scale, by the parity of p
+    double bterm[BS];  // per slot: its term of bib's sum over the list, init_v (p_IM e_v(x) m'[v] + p_ID d[v])
+    double ib[2];      // InsBegin of B.tables[p], in its column's scale, by the parity of p
     unsigned long long bc;
     LinParams lp;  // (read from here: the scalar registers are short)
 };
+// (the names the one-size block had)
+using WBCol = WBColT<WBK_T>;
+using WideBwdShared = WideBwdSharedT<WBK_T>;
 
-__device__ __forceinline__ uint32_t wb_hash(uint32_t id) { return (id * 2654435761u) >> 22; }
-__device__ __forceinline__ void wb_insert(WBCol &c, uint32_t id, int slot) {
-    uint32_t h = wb_hash(id);
+template <class Col> __device__ __forceinline__ uint32_t wb_hash(uint32_t id) { return (id * 2654435761u) >> Col::HASH_SHIFT; }
+template <class Col> __device__ __forceinline__ void wb_insert(Col &c, uint32_t id, int slot) {
+    uint32_t h = wb_hash<Col>(id);
     for (;;) {
         const uint32_t old = atomicCAS(&c.hkey[h], H_EMPTY, id);
         if (old == H_EMPTY) {
@@ -66,43 +79,43 @@ __device__ __forceinline__ void wb_insert(WBCol &c, uint32_t id, int slot) {
             return;
         }
         if (old == id) return;
-        h = (h + 1) & (WBK_HASH - 1);
+        h = (h + 1) & (Col::HASH - 1);
     }
 }
-__device__ __forceinline__ int wb_find(const WBCol &c, uint32_t id) {
-    uint32_t h = wb_hash(id);
+template <class Col> __device__ __forceinline__ int wb_find(const Col &c, uint32_t id) {
+    uint32_t h = wb_hash<Col>(id);
     for (;;) {
         const uint32_t k = c.hkey[h];
         if (k == id) return (int)c.hslot[h];
         if (k == H_EMPTY) return -1;
-        h = (h + 1) & (WBK_HASH - 1);
+        h = (h + 1) & (Col::HASH - 1);
     }
 }
 // (`par` alternates between two sets of wave results: one barrier per reduction)
-__device__ __forceinline__ double wb_block_max(WideBwdShared &sh, int &par, double v) {  // non-negative values
+template <class Sh> __device__ __forceinline__ double wb_block_max(Sh &sh, int &par, double v) {  // non-negative values
     v = wave_max(v);
     if ((threadIdx.x & 63) == 0) sh.red[par][threadIdx.x >> 6] = v;
     __syncthreads();
     double r = sh.red[par][0];
 #pragma unroll
-    for (int w = 1; w < WBK_WAVES; w++) r = fmax(r, sh.red[par][w]);
+    for (int w = 1; w < Sh::WAVES; w++) r = fmax(r, sh.red[par][w]);
     par ^= 1;
     return r;
 }
-__device__ __forceinline__ int wb_block_isum(WideBwdShared &sh, int &par, int v) {
+template <class Sh> __device__ __forceinline__ int wb_block_isum(Sh &sh, int &par, int v) {
     v = wave_isum(v);
     if ((threadIdx.x & 63) == 0) sh.wsum[par][threadIdx.x >> 6] = v;
     __syncthreads();
     int r = 0;
 #pragma unroll
-    for (int w = 0; w < WBK_WAVES; w++) r += sh.wsum[par][w];
+    for (int w = 0; w < Sh::WAVES; w++) r += sh.wsum[par][w];
     par ^= 1;
     return r;
 }
 
 // forward record of a position into sh.f*; false: missing (or larger than the class)
-__device__ __forceinline__ bool wb_load_record(const RecPool &p, uint64_t pos_index, WideBwdShared &sh, int &n, int &na,
-                                               int &E) {
+template <class Sh>
+__device__ __forceinline__ bool wb_load_record(const RecPool &p, uint64_t pos_index, Sh &sh, int &n, int &na, int &E) {
     const uint64_t o1 = p.off[pos_index];
     if (o1 == 0) return false;
     const uint8_t *rec = p.base + (o1 - 8);
@@ -110,7 +123,7 @@ __device__ __forceinline__ bool wb_load_record(const RecPool &p, uint64_t pos_in
     n = hw[0];
     na = hw[1];
     E = hw[2];
-    if (n > WBK_CAP) return false;
+    if (n > Sh::CAP) return false;
     const uint64_t idb = (uint64_t)((n + 1) & ~1) * 4;
     const uint32_t *ids = (const uint32_t *)(rec + 16);
     const double *m = (const double *)(rec + 16 + idb), *i = m + na, *d = i + na;
@@ -125,14 +138,14 @@ __device__ __forceinline__ bool wb_load_record(const RecPool &p, uint64_t pos_in
     return true;
 }
 
-__device__ __forceinline__ int wb_excl_scan(WideBwdShared &sh, int &par, int v, int &total) {
+template <class Sh> __device__ __forceinline__ int wb_excl_scan(Sh &sh, int &par, int v, int &total) {
     const int inc = wave_iscan(v);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 63) sh.wsum[par][w] = inc;
     __syncthreads();
     int pre = 0, tt = 0;
 #pragma unroll
-    for (int k = 0; k < WBK_WAVES; k++) {
+    for (int k = 0; k < Sh::WAVES; k++) {
         const int x = sh.wsum[par][k];
         tt += x;
         pre += k < w ? x : 0;
@@ -144,8 +157,8 @@ __device__ __forceinline__ int wb_excl_scan(WideBwdShared &sh, int &par, int v, 
 
 // emit_mapping (mapping_flow.hip) with by_node = true, topk = 0: val[0..n) -> the list record of a position.  Only the
 // entries that stay are sorted (a column next to a wide spot has 400 entries of which a few dozen stay).
-__device__ __forceinline__ bool wb_emit(const RecPool &mp, uint64_t pos_index, WideBwdShared &sh, int &par, int n,
-                                        double ratio_lin) {
+template <class Sh>
+__device__ __forceinline__ bool wb_emit(const RecPool &mp, uint64_t pos_index, Sh &sh, int &par, int n, double ratio_lin) {
     const int t = threadIdx.x;
     const double v = t < n ? sh.dA[t] : 0.0;
     double *val = sh.dB;       // the list being built: log values ...
@@ -160,7 +173,7 @@ __device__ __forceinline__ bool wb_emit(const RecPool &mp, uint64_t pos_index, W
         val[at] = log(v);
         ids[at] = sh.fid[t];
     }
-    for (int k = t; k < NP; k += WBK_T)
+    for (int k = t; k < NP; k += Sh::T)
         if (k >= keep) {
             val[k] = -INFINITY;
             ids[k] = 0xffffffffu;
@@ -192,12 +205,75 @@ __device__ __forceinline__ bool wb_emit(const RecPool &mp, uint64_t pos_index, W
 struct WideBwdListArgs : SparseBwdArgs {
     unsigned long long *cells;
 };
-template <bool LIST> using WideBwdArgsOf = typename std::conditional<LIST, WideBwdListArgs, SparseBwdArgs>::type;
+// ... and those of its transition-posterior form
+struct WideBwdEdgeArgs : SparseBwdEdgeArgs {
+    unsigned long long *cells;
+};
+template <bool LIST, bool EDGES>
+using WideBwdArgsOf = typename std::conditional<LIST, typename std::conditional<EDGES, WideBwdEdgeArgs, WideBwdListArgs>::type,
+                                                SparseBwdArgs>::type;
 
-// (LIST: 4 waves per SIMD -- 128 VGPRs -- let two blocks share a CU, as the adaptive flavour's 127 do unasked)
-template <bool LIST = false>
-__global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(const WideBwdArgsOf<LIST> a) {
-    __shared__ WideBwdShared sh;
+// (EDGES) The edge terms of merged index i for the forward entry in slot j of sh.f* (emit_edge_terms, mapping_flow.hip,
+// thread = slot), one per child of the node in the CSR's order:
+//   to Match (i < len): t e_l(x[i]) B.table_merged(i+1).m[l] (p_MM F.m[k] + p_IM F.i[k] + p_DM F.d[k]) / P   (weight wM)
+//   to Del:             t           B.table_merged(i).d[l]   (p_MD F.m[k] + p_ID F.i[k] + p_DD F.d[k]) / P   (weight wD)
+// prev_init: B.table_merged(i+1) is b_init, m = p_end on every node; i_is_len: the Del target is b_init (d = p_end), no
+// Match term.  Returns the number of non-zero terms; STORE: writes them into the record from slot w on, keys = edge ids.
+// The block counts first and stores after the scan of the counts: the terms are computed twice instead of held in
+// registers across the scan (the kernel sits at its 128 VGPRs).
+template <bool STORE, class Sh, class Col>
+__device__ __forceinline__ int wb_edge_terms(const SparseBwdEdgeArgs &a, const Sh &sh, int j, const Col &prev, bool prev_init,
+                                             const Col &cur, bool i_is_len, uint8_t x, double wM, double wD, uint64_t w) {
+    const SparseModel &M = a.M;
+    const LinParams &lp = sh.lp;
+    const uint32_t k = sh.fid[j];
+    const double fm = sh.fm[j], fi = sh.fi[j], fd = sh.fd[j];
+    const double sm = lp.p_MM * fm + lp.p_IM * fi + lp.p_DM * fd;
+    const double sd = lp.p_MD * fm + lp.p_ID * fi + lp.p_DD * fd;
+    const uint32_t a0 = M.chi_off[k], deg = M.chi_off[k + 1] - a0;
+    int c = 0;
+#pragma unroll 1
+    for (uint32_t q = 0; q < deg; q++) {
+        const double tw = M.chi_w[a0 + q];
+        const uint32_t l = M.chi_node[a0 + q];
+        double term = 0.0;
+        if (!i_is_len) {
+            double bm = lp.p_end;
+            if (!prev_init) {
+                const int ps = wb_find(prev, l);
+                bm = ps >= 0 ? prev.m[ps] : 0.0;
+            }
+            // (a zero factor stays zero whatever the weight: no 0 * inf)
+            const double v1 = sm * (M.emis[l] == x ? lp.p_match : lp.p_mismatch) * bm;
+            if (v1 != 0.0) term += v1 * wM;
+        }
+        double bd = lp.p_end;
+        if (!i_is_len) {
+            const int cs = wb_find(cur, l);
+            bd = cs >= 0 ? cur.d[cs] : 0.0;
+        }
+        const double v2 = sd * bd;
+        if (v2 != 0.0) term += v2 * wD;
+        const double val = tw * term;
+        if (val != 0.0) {
+            if (STORE) {
+                a.rec_key[w + c] = M.chi_edge[a0 + q];
+                a.rec_val[w + c] = val;
+            }
+            c++;
+        }
+    }
+    return c;
+}
+
+// (LIST: 4 waves per SIMD -- 128 VGPRs -- let two blocks of 448 share a CU, as the adaptive flavour's 127 do unasked)
+template <bool LIST = false, bool EDGES = false, int BS = WBK_T>
+__global__ void __launch_bounds__(BS, LIST ? 4 : 1) wide_backward_kernel(const WideBwdArgsOf<LIST, EDGES> a) {
+    static_assert(LIST || (!EDGES && BS == WBK_T), "the adaptive flavour has one size and no edge terms");
+    static_assert(BS == WBK_T || BS == WBK_T_SMALL, "two block sizes");
+    using Sh = WideBwdSharedT<BS>;
+    using Col = WBColT<BS>;
+    __shared__ Sh sh;
     const int t = threadIdx.x;
     const uint32_t gi = a.lanes[blockIdx.x];
     const int g = (int)(gi / a.W), r = (int)(gi % a.W);
@@ -222,12 +298,27 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
     int E0 = 0;
     bool done0 = false;
     unsigned long long n_cells = 0;
+    uint64_t end_fill = 0;  // (EDGES) entries of merged index len, at the head of the record of position len-1
     if (LIST || a.mode == 0) {
         pos = len - 1;
         // merged index len: F.tables[len-1] (.) b_init / P   (table.rs:414-434, backward.rs:197-211)
         if (!wb_load_record(a.fpool, p0 + (uint64_t)(len - 1), sh, fn, fna, fE)) {
             stopped = true;  // missing: nothing done
             stop_at = len;
+        } else if constexpr (EDGES) {
+            // merged index len (Del into b_init only) opens the record of position len-1 (freq.rs:276-298)
+            const uint64_t rq = q0 + (uint64_t)(len - 1);
+            const uint64_t base = a.rec_off[rq], cap = a.rec_off[rq + 1] - base;
+            const double wD = ok ? exp((double)fE * SP_LN2 - logP) : 0.0;
+            int cnt = 0;
+            if (ok && t < fn) cnt = wb_edge_terms<false>(a, sh, t, sh.col[0], true, sh.col[0], true, 0, 0.0, wD, 0);
+            int tot;
+            const int at = wb_excl_scan(sh, par, cnt, tot);
+            if ((uint64_t)tot > cap) err |= SP_ERR_CAPACITY;  // (cannot happen: the bound is exact; nothing is written past the record)
+            else {
+                if (cnt) wb_edge_terms<true>(a, sh, t, sh.col[0], true, sh.col[0], true, 0, 0.0, wD, base + (uint64_t)at);
+                end_fill = (uint64_t)tot;
+            }
         } else {
             const double w = ok ? exp((double)fE * SP_LN2 - logP) * lp.p_end : 0.0;
             if (t < fn) sh.dA[t] = w * (sh.fm[t] + sh.fi[t] + sh.fd[t]);
@@ -239,9 +330,9 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
         if (pos < len - 1) {
             // B.tables[pos+1] from the hand-off slot
             const BHandoff &h = a.hand[gi];
-            WBCol &c = sh.col[(pos + 1) & 1];
+            Col &c = sh.col[(pos + 1) & 1];
             const int n = h.n;
-            for (int k = t; k < WBK_HASH; k += WBK_T) c.hkey[k] = H_EMPTY;
+            for (int k = t; k < Col::HASH; k += BS) c.hkey[k] = H_EMPTY;
             if (t == 0) {
                 c.n = n;
                 c.E = h.E;
@@ -274,7 +365,7 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
             // mapping.nodes(pos) (backward.rs:59-90)
             const uint64_t l0 = a.list_off[q0 + (uint64_t)pos];
             nl = (int)(a.list_off[q0 + (uint64_t)pos + 1] - l0);
-            if (nl > WBK_CAP) {  // (the same for every thread)
+            if (nl > Sh::CAP) {  // (the same for every thread)
                 err |= SP_ERR_CAPACITY;
                 break;
             }
@@ -284,7 +375,7 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
             // filled_nodes (table.rs:117-123): the record's elements by total, stable (sort_desc, frontier_dev.h)
             {
                 const int NP = bitonic_size(fn);
-                for (int k = t; k < NP; k += WBK_T) {
+                for (int k = t; k < NP; k += BS) {
                     val[k] = k < fn ? sh.fm[k] + sh.fi[k] + sh.fd[k] : -1.0;
                     order[k] = (uint16_t)k;
                 }
@@ -295,11 +386,11 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
         }
         __syncthreads();
         // ---- one backward column over the list (bwd_list_step, sparse_dev.h)
-        const WBCol &prev = sh.col[(pos + 1) & 1];
-        WBCol &cur = sh.col[pos & 1];
+        const Col &prev = sh.col[(pos + 1) & 1];
+        Col &cur = sh.col[pos & 1];
         const bool prev_is_init = pos == len - 1;
         const uint8_t x = a.bases[((size_t)g * a.Lb + pos) * a.W + r];
-        for (int k = t; k < WBK_HASH; k += WBK_T) cur.hkey[k] = H_EMPTY;
+        for (int k = t; k < Col::HASH; k += BS) cur.hkey[k] = H_EMPTY;
         if (t == 0) cur.n = nl;
         __syncthreads();
         BwdAdj rec;
@@ -401,7 +492,7 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
         if (t < 64) {  // (wave 0: the next barrier publishes sh.ib[pos & 1])
             double part = 0.0;
 #pragma unroll 1
-            for (int w = 0; w < WBK_WAVES; w++) {
+            for (int w = 0; w < Sh::WAVES; w++) {
                 const int k = t + 64 * w;
                 if (k < nl) part += sh.bterm[k];
             }
@@ -410,7 +501,7 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
             if (LIST && pos == 0) {
                 double pm = 0.0;
 #pragma unroll 1
-                for (int w = 0; w < WBK_WAVES; w++) {
+                for (int w = 0; w < Sh::WAVES; w++) {
                     const int k = t + 64 * w;
                     if (k < nl) pm += sh.fm[k];
                 }
@@ -419,11 +510,63 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
         }
         if constexpr (LIST) {
             n_cells += (unsigned long long)nl;
+            if constexpr (EDGES) {
+                // merged index pos: sh.f* = F.tables[pos-1], cur = B.tables[pos], prev = B.tables[pos+1] (b_init at len-1).
+                // Edge terms by forward entry (none at pos 0), then the Begin terms (emit_begin_terms, mapping_flow.hip) by
+                // slot of cur, then of prev unless it is b_init (dense there: the host adds it):
+                //   to Del:   c_D init_v B.tables[pos].d[v] / P;   to Match: c_M init_v e_v(x[pos]) B.tables[pos+1].m[v] / P
+                // with (c_M, c_D) = (p_MM, p_MD) at pos 0 and ib_{pos-1} (p_IM, p_ID) after, the chain in the exponent.
+                const uint64_t rq = q0 + (uint64_t)pos;
+                const uint64_t base = a.rec_off[rq], cap = a.rec_off[rq + 1] - base;
+                const uint64_t fill = prev_is_init ? end_fill : 0;
+                double bcur = 0.0, bprev = 0.0, wM = 0.0, wD = 0.0;
+                int cnt = 0;
+                if (ok) {
+                    const int Eprev = prev_is_init ? 0 : prev.E;
+                    if (pos > 0) {
+                        wM = exp((double)(fE + Eprev) * SP_LN2 - logP);
+                        wD = exp((double)(fE + Ecur) * SP_LN2 - logP);
+                        if (t < fn) cnt = wb_edge_terms<false>(a, sh, t, prev, prev_is_init, cur, false, x, wM, wD, 0);
+                    }
+                    const double lib = pos == 0 ? 0.0 : a.M.logib[pos - 1];
+                    const double cM = pos == 0 ? lp.p_MM : lp.p_IM, cD = pos == 0 ? lp.p_MD : lp.p_ID;
+                    if (t < nl) {
+                        const double v2 = a.M.init[cur.id[t]] * cD * cur.d[t];
+                        if (v2 != 0.0) bcur = v2 * exp(lib + (double)Ecur * SP_LN2 - logP);
+                    }
+                    if (!prev_is_init && t < prev.n) {
+                        const uint32_t v = prev.id[t];
+                        const double v1 = a.M.init[v] * cM * (a.M.emis[v] == x ? lp.p_match : lp.p_mismatch) * prev.m[t];
+                        if (v1 != 0.0) bprev = v1 * exp(lib + (double)Eprev * SP_LN2 - logP);
+                    }
+                }
+                // one scan for the three groups: edge terms in bits 0-11 (at most ADJ_DEG x 448 = 2240), cur's and prev's Begin
+                // terms in bits 12-21 and 22-31 (at most 448 each)
+                int tot;
+                const int at = wb_excl_scan(sh, par, cnt | (bcur != 0.0 ? 1 << 12 : 0) | (bprev != 0.0 ? 1 << 22 : 0), tot);
+                const uint64_t nE = (uint64_t)(tot & 0xfff), nC = (uint64_t)((tot >> 12) & 0x3ff), nP = (uint64_t)((tot >> 22) & 0x3ff);
+                if (fill + nE + nC + nP > cap) err |= SP_ERR_CAPACITY;  // (cannot happen: the bound is exact)
+                else {
+                    if (cnt) wb_edge_terms<true>(a, sh, t, prev, prev_is_init, cur, false, x, wM, wD, base + fill + (uint64_t)(at & 0xfff));
+                    if (bcur != 0.0) {
+                        const uint64_t w = base + fill + nE + (uint64_t)((at >> 12) & 0x3ff);
+                        a.rec_key[w] = a.E + cur.id[t];
+                        a.rec_val[w] = bcur;
+                    }
+                    if (bprev != 0.0) {
+                        const uint64_t w = base + fill + nE + nC + (uint64_t)((at >> 22) & 0x3ff);
+                        a.rec_key[w] = a.E + prev.id[t];
+                        a.rec_val[w] = bprev;
+                    }
+                    if (t == 0) a.rec_cnt[rq] = fill + nE + nC + nP;
+                }
+            }
             if (pos == 0) {  // column 0 has no F.tables[-1]: nothing to emit
                 E0 = Ecur;
                 done0 = true;
                 break;
             }
+            if constexpr (EDGES) continue;  // no mapping list
         }
         // S = F.tables[pos-1] (.) B.tables[pos] / P over F's elements (table.rs:320-345, 500-505)
         const double w = ok ? exp((double)(fE + Ecur) * SP_LN2 - logP) : 0.0;
@@ -451,7 +594,7 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
     } else if (stopped && !err) {
         // park B.tables[stop_at + 1] for the next phase
         if (have_cols && stop_at < len) {
-            const WBCol &c = sh.col[(stop_at + 1) & 1];
+            const Col &c = sh.col[(stop_at + 1) & 1];
             BHandoff &h = a.hand[gi];
             if (c.n > HANDOFF_CAP) err |= SP_ERR_CAPACITY;
             else {
@@ -472,7 +615,7 @@ __global__ void __launch_bounds__(WBK_T, LIST ? 4 : 1) wide_backward_kernel(cons
     } else if (!err) {
         // hand B.tables[s0+1] to the dense backward kernel: dense column (zeros elsewhere), its exponent and maximum
         if (have_cols) {
-            const WBCol &c = sh.col[(s0 + 1) & 1];
+            const Col &c = sh.col[(s0 + 1) & 1];
             const size_t NW = (size_t)a.d.N * a.W;
             const int pc = (s0 + 1) & 1;
             double *bm = a.d.Bm + ((size_t)g * a.d.bcols + pc) * NW;

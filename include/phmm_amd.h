@@ -387,7 +387,15 @@ int phmm_run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const ph
  * list entries of its reads) and, for phmm_generate_mappings with use_max_ratio, the
  * list backward on a block (one launch; cells = list entries of the positions it
  * computed).  The developer knob PHMM_NO_WIDE_LIST_BWD=1 keeps that backward on the
- * generic kernel while the forward stays on the block.  Any other index is PHMM_EINVAL. */
+ * generic kernel while the forward stays on the block.  With PHMM_WIDE_EDGE_BWD=1 beside
+ * PHMM_WIDE_HINTED=1, phmm_run_with_mapping_edges runs its backward half on a block as
+ * well and adds that half's launches and cells (list entries of the positions it
+ * computed) to index 4; without that knob the call counts its forward half alone.
+ * PHMM_WIDE_BWD_T=128 sends the reads of a block backward whose longest list holds at most
+ * 128 nodes to a block of 128 threads (one more launch, the same cells, the same bits);
+ * PHMM_WIDE_BWD_T=448 keeps every such read on the block of 448.  Unset, the library takes
+ * the small block when a call has more such reads than twice the device's compute units.
+ * Any other index is PHMM_EINVAL. */
 int phmm_last_call_stats(int which, double *out_ms, uint64_t *out_launches,
                          uint64_t *out_cells);
 int phmm_enable_timing(int on);

@@ -2,17 +2,23 @@
 classes on a block switched off and on, in ONE process:
 
   lists   generate_mappings(reads, mappings, use_max_ratio = True) on the lists of a generate_mappings(None) call
-  edges   run_with_mapping_edge_freqs on the same lists (its forward half only can run on the block)
+  edges   run_with_mapping_edge_freqs on the same lists
 
-    python tools/list_pass_wide_time.py [--workloads rep20,cfg3] [--reps 7] [--warmup 2]
+    python tools/list_pass_wide_time.py [--workloads rep20,cfg3,u100] [--reps 7] [--warmup 2] [--coverage 20]
+
+rep20 and cfg3 are bench.py's workloads; u100 and u20 are tests/repeat_cases.py's data sets of those names at k = 40 (a
+100 bp unit x 10 and a 20 bp unit x 50: the short lists of wide reads, the range of the 128-thread backward block);
+--coverage is their read depth (20 as the tests build them: 79 reads; 1000: some 4000 reads, more blocks than a device holds).
 
 Per workload and call, after `--warmup` calls of every variant (workspace growth, code objects), the variants take turns
 `--reps` times: `off` (PHMM_NO_WIDE_HINTED=1: the generic one-wave kernels, the default's launches), `fwd`
-(PHMM_WIDE_HINTED=1 PHMM_NO_WIDE_LIST_BWD=1: block forward, generic backward) and `on` (PHMM_WIDE_HINTED=1: both halves
-on the block; for `edges` the same as `fwd`, left out).  The knobs are read at every call.  Prints one JSON line per
-workload and call: wall ms of each repetition per variant (host clock around the synchronous call), median, minimum
-and maximum, phmm_last_call_stats(4) of the last call of each variant, and checksums that show every variant computed
-the same thing.
+(PHMM_WIDE_HINTED=1 PHMM_NO_WIDE_LIST_BWD=1: block forward, generic backward), `on` (lists: PHMM_WIDE_HINTED=1, both
+halves on the block; for `edges` that is `fwd`, left out), `edges_on` (edges: PHMM_WIDE_HINTED=1 PHMM_WIDE_EDGE_BWD=1,
+both halves on the block) and `on128` / `on448` (both halves on the block with PHMM_WIDE_BWD_T=128 / 448: the backward
+block's size for reads whose longest list holds at most 128 nodes).  The knobs are read at every call.  Prints one JSON
+line per workload and call: the spread of the longest list per read (which block size a read takes), wall ms of each
+repetition per variant (host clock around the synchronous call), median, minimum and maximum, phmm_last_call_stats(4) of
+the last call of each variant, and checksums that show every variant computed the same thing.
 """
 import argparse
 import json
@@ -29,8 +35,11 @@ VARIANTS = {
     "off": {"PHMM_NO_WIDE_HINTED": "1"},
     "fwd": {"PHMM_WIDE_HINTED": "1", "PHMM_NO_WIDE_LIST_BWD": "1"},
     "on": {"PHMM_WIDE_HINTED": "1"},
+    "edges_on": {"PHMM_WIDE_HINTED": "1", "PHMM_WIDE_EDGE_BWD": "1"},
+    "on128": {"PHMM_WIDE_HINTED": "1", "PHMM_WIDE_EDGE_BWD": "1", "PHMM_WIDE_BWD_T": "128"},
+    "on448": {"PHMM_WIDE_HINTED": "1", "PHMM_WIDE_EDGE_BWD": "1", "PHMM_WIDE_BWD_T": "448"},
 }
-KNOBS = ("PHMM_WIDE_HINTED", "PHMM_NO_WIDE_HINTED", "PHMM_NO_WIDE_LIST_BWD")
+KNOBS = ("PHMM_WIDE_HINTED", "PHMM_NO_WIDE_HINTED", "PHMM_NO_WIDE_LIST_BWD", "PHMM_WIDE_EDGE_BWD", "PHMM_WIDE_BWD_T")
 
 
 def main():
@@ -38,6 +47,7 @@ def main():
     ap.add_argument("--workloads", default="rep20,cfg3")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--coverage", type=int, default=20, help="read depth of the u100 / u20 data sets")
     args = ap.parse_args()
     import bench
     import dbgphmm_amd as D
@@ -61,7 +71,12 @@ def main():
         return ms, out, {"ms": round(st[0], 3), "launches": int(st[1]), "cells": int(st[2])}
 
     for name in args.workloads.split(","):
-        arrays, reads, _ = bench.build_workload(name)
+        if name in ("u100", "u20"):
+            sys.path.insert(0, os.path.join(HERE, "tests"))
+            from repeat_cases import dataset
+            arrays, reads, _, _ = dataset(name, 40, coverage=args.coverage)
+        else:
+            arrays, reads, _ = bench.build_workload(name)
         gm, rc = D.PHMMModel(arrays), D.ReadCollection(reads)
         for k in KNOBS:
             os.environ.pop(k, None)
@@ -78,7 +93,8 @@ def main():
             lf, ef, inf = gm.run_with_mapping_edge_freqs(rc, mp)
             return [float(lf.sum()), float(ef.sum()), float(inf.sum())]
 
-        for call, fn, variants in (("lists", lists, ("off", "fwd", "on")), ("edges", edges, ("off", "fwd"))):
+        for call, fn, variants in (("lists", lists, ("off", "fwd", "on", "on128", "on448")),
+                                   ("edges", edges, ("off", "fwd", "edges_on", "on128", "on448"))):
             for _ in range(args.warmup):
                 for v in variants:
                     under(v, fn)
@@ -92,6 +108,9 @@ def main():
             print(json.dumps({
                 "workload": name, "call": call, "reads": len(reads), "n_nodes": int(arrays.n_nodes),
                 "reads_with_lists_65_400": int(((rmax > 64) & (rmax <= 400)).sum()), "list_entries": int(po[-1]),
+                "read_max_list": {"min": int(rmax.min()), "median": float(np.median(rmax)), "max": int(rmax.max()),
+                                  "at_most_64": int((rmax <= 64).sum()), "65_128": int(((rmax > 64) & (rmax <= 128)).sum()),
+                                  "129_400": int(((rmax > 128) & (rmax <= 400)).sum())},
                 "ms": ms,
                 "median_min_max": {v: [round(float(np.median(x)), 3), min(x), max(x)] for v, x in ms.items()},
                 "last": last}), flush=True)
