@@ -100,6 +100,7 @@ def lib():
         "phmm_likelihood_current_groups": (i32, [vp, vp]),
         "phmm_generate_mappings": (i32, [vp, vp, vp, i32, P(vp), vp]),
         "phmm_run_with_mapping_edges": (i32, [vp, vp, vp, vp, vp, vp]),
+        "phmm_run_with_mapping_states": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_last_call_stats": (i32, [i32, P(dbl), P(u64), P(u64)]),
         "phmm_enable_timing": (i32, [i32]),
     }
@@ -127,6 +128,10 @@ DECLARED_SYMBOLS = [
     "phmm_likelihood_set_groups", "phmm_likelihood_score_group_changes", "phmm_likelihood_move_groups",
     "phmm_likelihood_current_groups",
 ]
+
+# entry points declared in companion headers of include/phmm_amd.h (whose own symbol table, DECLARED_SYMBOLS, is closed):
+# header -> symbols.  lib() binds them with the rest.
+EXTENSION_SYMBOLS = {"phmm_amd_states.h": ["phmm_run_with_mapping_states"]}
 
 
 def check(rc: int) -> None:

@@ -71,6 +71,7 @@ void refresh_knobs() {
     k.wide_hinted = flag("PHMM_WIDE_HINTED") && !k.no_wide_hinted;
     k.no_wide_list_bwd = flag("PHMM_NO_WIDE_LIST_BWD");
     k.wide_edge_bwd = flag("PHMM_WIDE_EDGE_BWD");
+    k.wide_states_bwd = flag("PHMM_WIDE_STATES_BWD");
     k.wide_bwd_t = num("PHMM_WIDE_BWD_T", 0);
     if (k.wide_bwd_t != 128 && k.wide_bwd_t != 448) k.wide_bwd_t = 0;
     k.wide_hinted_cpb = num("PHMM_WIDE_HINTED_CPB", 0);
@@ -1009,6 +1010,16 @@ int phmm_run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const ph
             return;
         }
         run_with_mapping_edges(m, reads, mp, out_lf, out_ef, out_if);
+    });
+}
+
+int phmm_run_with_mapping_states(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_lf,
+                                 double *out_state_logp, uint32_t *out_best) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        check_mapping_nodes(m, mp, reads);
+        if (reads->R == 0) return;
+        run_with_mapping_states(m, reads, mp, out_lf, out_state_logp, out_best);
     });
 }
 

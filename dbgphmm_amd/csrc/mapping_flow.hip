@@ -266,8 +266,70 @@ __device__ __forceinline__ uint64_t emit_begin_terms(const SparseBwdEdgeArgs &a,
     return fill;
 }
 
-template <int CAP, bool EDGES = false>
-__global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgsOf<EDGES> a) {
+// ---- state posteriors over the lists: sparse_backward_kernel<CAP, false, true>
+// PHMMOutput::to_emit_probs of one merged index by state (table.rs:500-505) over the entries of the INPUT list of read
+// position rq, the position the index belongs to: fr = F.tables[p], b = B.tables[p+1] (null: b_init, p_end in every
+// state of every node, exponent 0; backward.rs:197-211).  The product keeps the forward's elements (table.rs:320-331), so
+// every list entry gets its three values: -inf where the forward record does not hold its node or B does not (a node
+// that left the list).  The record's slot of a list entry is looked up -- its own slot first, which is where the list
+// forwards put it, then the whole record: nothing here relies on the record keeping the list's order.  `list` is the
+// kernel's list buffer, free between two column steps (the next step loads this very list into it).
+// The head of to_states() of the position is reduced over (value, kind, slot) in registers.
+template <int CAP>
+__device__ __forceinline__ void emit_states(const SparseBwdStatesArgs &a, uint64_t rq, const FRec<CAP> &fr, const Col<CAP> *b,
+                                            double logP, bool ok, uint32_t *list, uint32_t &err) {
+    const int lane = threadIdx.x;
+    const uint64_t l0 = a.list_off[rq];
+    const int nl = (int)(a.list_off[rq + 1] - l0);
+    if (nl > CAP) {  // (cannot happen: the classes are split by the longest list of a read; nothing is written past `list`)
+        err |= SP_ERR_CAPACITY;
+        return;
+    }
+    for (int s = lane; s < nl; s += 64) list[s] = a.list_nodes[l0 + s];
+    wave_sync();
+    const double pend = a.M.lp.p_end;
+    const double w = (double)(fr.E + (b ? b->E : 0)) * SP_LN2 - logP;
+    const int fn = fr.n;
+    double bv = -INFINITY;
+    int br = -1;
+    for (int s = lane; s < nl; s += 64) {
+        const uint32_t v = list[s];
+        int j = s < fn && fr.id[s] == v ? s : -1;
+        for (int q = 0; j < 0 && q < fn; q++)
+            if (fr.id[q] == v) j = q;
+        double lm = -INFINITY, li = -INFINITY, ld = -INFINITY;
+        if (ok && j >= 0) {
+            double bm = pend, bi = pend, bd = pend;
+            if (b) {
+                const int bs = hash_find(*b, v);
+                bm = bs >= 0 ? b->m[bs] : 0.0;
+                bi = bs >= 0 ? b->i[bs] : 0.0;
+                bd = bs >= 0 ? b->d[bs] : 0.0;
+            }
+            lm = st_log(fr.m[j], bm, w);
+            li = st_log(fr.i[j], bi, w);
+            ld = st_log(fr.d[j], bd, w);
+        }
+        if (a.st_logp) {
+            double *o = a.st_logp + 3 * (l0 + (uint64_t)s);
+            o[0] = lm;
+            o[1] = li;
+            o[2] = ld;
+        }
+        st_take(bv, br, lm, s);
+        st_take(bv, br, li, ST_RANK + s);
+        st_take(bv, br, ld, 2 * ST_RANK + s);
+    }
+    if (a.st_best) {
+        st_wave_best(bv, br);
+        if (lane == 0) a.st_best[rq] = st_code(br);
+    }
+    wave_sync();  // (fr and `list` are loaded anew by the next step)
+}
+
+template <int CAP, bool EDGES = false, bool STATES = false>
+__global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgsOf<EDGES, STATES> a) {
+    static_assert(!(EDGES && STATES), "one flavour at a time");
     __shared__ FRec<CAP> fr;
     __shared__ Col<CAP> cols[2];
     __shared__ double dA[CAP], dB[CAP];
@@ -307,6 +369,8 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
             if (ok)
                 end_fill = emit_edge_terms<CAP>(a, fr, cols[0], true, cols[0], true, 0, logP, a.rec_off[rq], 0,
                                                 a.rec_off[rq + 1] - a.rec_off[rq], err);
+        } else if constexpr (STATES) {
+            emit_states<CAP>(a, q0 + (uint64_t)(len - 1), fr, nullptr, logP, ok, list, err);
         } else {
             const double w = ok ? exp((double)fr.E * SP_LN2 - logP) * lp.p_end : 0.0;
             for (int j = lane; j < fr.n; j += 64) val[j] = w * (fr.m[j] + fr.i[j] + fr.d[j]);
@@ -387,6 +451,12 @@ __global__ void __launch_bounds__(64) sparse_backward_kernel(const SparseBwdArgs
             }
             if (lane == 0) a.rec_cnt[rq] = fill;
             if (pos == 0) break;
+            continue;  // no mapping list
+        }
+        if constexpr (STATES) {
+            // merged index pos >= 1 belongs to read position pos-1: fr = F.tables[pos-1], cur = B.tables[pos]
+            if (pos == 0) break;
+            emit_states<CAP>(a, q0 + (uint64_t)(pos - 1), fr, &cur, logP, ok, list, err);
             continue;  // no mapping list
         }
         if (pos == 0) break;  // (list mode) column 0 has no F.tables[-1]: nothing to emit
@@ -1775,9 +1845,9 @@ static void hinted_list_pass_setup(phmm_model *m, const phmm_reads *reads, const
 // blocks run side by side, and seven small ones fit a CU; with fewer, a launch lasts as long as its longest read and a
 // second launch only adds its own (slower at 26 and 60 such reads, faster at 3007).
 // Index 4 of the statistics counts the launches.
-template <bool EDGES>
+template <bool EDGES, bool STATES = false>
 static void launch_wide_list_backward(const phmm_mappings *mp_in, const std::vector<uint32_t> &wb, uint32_t *d_lanes,
-                                      const WideBwdArgsOf<true, EDGES> &wa) {
+                                      const WideBwdArgsOf<true, EDGES, STATES> &wa) {
     hipStream_t s = current_stream();
     CallStats &st = stats();
     size_t n_small = 0;
@@ -1797,8 +1867,8 @@ static void launch_wide_list_backward(const phmm_mappings *mp_in, const std::vec
         LaunchTimer lt(timing_enabled());
         HIP_CHECK(hipMemcpyAsync(d_lanes, who.data(), sizeof(uint32_t) * who.size(), hipMemcpyHostToDevice, s));
         lt.begin();
-        if (c == 0) hipLaunchKernelGGL((wide_backward_kernel<true, EDGES, WBK_T>), dim3((unsigned)who.size()), dim3(WBK_T), 0, s, wa);
-        else hipLaunchKernelGGL((wide_backward_kernel<true, EDGES, WBK_T_SMALL>), dim3((unsigned)who.size()), dim3(WBK_T_SMALL), 0, s, wa);
+        if (c == 0) hipLaunchKernelGGL((wide_backward_kernel<true, EDGES, WBK_T, STATES>), dim3((unsigned)who.size()), dim3(WBK_T), 0, s, wa);
+        else hipLaunchKernelGGL((wide_backward_kernel<true, EDGES, WBK_T_SMALL, STATES>), dim3((unsigned)who.size()), dim3(WBK_T_SMALL), 0, s, wa);
         lt.end();
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));  // the lane list is reused by the next launch
@@ -2111,6 +2181,86 @@ void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_m
     trace("edge freqs");
     if (out_ef && E) copy_out(out_ef, freq, sizeof(double) * E);
     if (out_if) copy_out(out_if, freq + E, sizeof(double) * N);
+    put_doubles(out_lf, lf.data(), R);
+}
+
+// ---------------------------------------------------------------- run_with_mapping + to_emit_probs by state
+// PHMMModel::run_with_mapping (freq.rs:72-76) of every read on its lists, then per read position p
+// PHMMOutput::to_emit_probs(p + 1) by state (table.rs:500-505) and the head of its to_states() (table.rs:215-254).  The
+// front half is that of run_with_mapping_edges: the record-storing list forward and the class split of the reads.  The
+// list pass (sparse_backward_kernel<CAP, false, true>) holds at step pos F.tables[pos-1] and B.tables[pos], the two
+// factors of merged index pos, and writes the three logs of every entry of the INPUT list of position pos-1 (index len
+// against b_init at its start): every entry of every position is written once, by one kernel, so nothing is cleared and
+// nothing depends on the timing.  A device output is written in place; a host output through a staging buffer of the
+// workspace, which goes back when the call ends.
+void run_with_mapping_states(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
+                             double *out_sl, uint32_t *out_best) {
+    hipStream_t s = current_stream();
+    const uint64_t R = reads->R, n_pos = reads->total, n_ent = mp_in->total_entries;
+    struct ReleaseScratch {
+        phmm_model *m;
+        ~ReleaseScratch() {
+            for (int i : {5, 17}) m->wset().aux[i].release();
+        }
+    } release_scratch{m};
+    std::vector<double> lf;
+    SparseBwdStatesArgs ba{};
+    std::vector<uint32_t> cls[2];
+    unsigned long long *d_cells = nullptr;
+    hinted_list_pass_setup(m, reads, mp_in, lf, ba, cls, &d_cells);
+    ba.logb = nullptr;
+    auto on_device = [](const void *p) {
+        hipPointerAttribute_t at;
+        const bool dev = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
+        if (!dev) (void)hipGetLastError();
+        return dev;
+    };
+    DevBuf &d_sl = m->wset().aux[5], &d_best = m->wset().aux[17];
+    const bool stage_sl = out_sl && n_ent && !on_device(out_sl), stage_best = out_best && n_pos && !on_device(out_best);
+    if (stage_sl) d_sl.reserve(sizeof(double) * 3 * n_ent);  // (PHMM_ENOMEM if the device cannot give it)
+    if (stage_best) d_best.reserve(sizeof(uint32_t) * n_pos);
+    ba.st_logp = stage_sl ? d_sl.as<double>() : out_sl;
+    ba.st_best = stage_best ? d_best.as<uint32_t>() : out_best;
+    uint32_t *const d_lanes = const_cast<uint32_t *>(ba.lanes);
+    // lists of 65-400 nodes on a block (wide_backward_kernel<true, false, BS, true>, wide_bwd_kernel.h): packed adjacency
+    // records only, and opt-in beside the forward's block class (PHMM_WIDE_STATES_BWD).  A read the block flags is rerun
+    // by the generic kernel, which rewrites the read's entries and reports what it finds
+    if (knobs().wide_hinted && knobs().wide_states_bwd && !knobs().no_wide_list_bwd && m->dev.max_degree <= (uint32_t)ADJ_DEG) {
+        std::vector<uint32_t> wb, rest;
+        for (uint32_t r : cls[1]) (mp_in->read_max_list[r] <= (uint32_t)WBK_CAP ? wb : rest).push_back(r);
+        if (!wb.empty()) {
+            WideBwdStatesArgs wa{};
+            static_cast<SparseBwdStatesArgs &>(wa) = ba;
+            wa.cells = d_cells;
+            launch_wide_list_backward<false, true>(mp_in, wb, d_lanes, wa);
+            unsigned long long h_cells = 0;
+            HIP_CHECK(hipMemcpy(&h_cells, d_cells, sizeof(h_cells), hipMemcpyDeviceToHost));
+            stats().cells[4] += h_cells;
+            std::vector<uint32_t> herr(R);
+            HIP_CHECK(hipMemcpy(herr.data(), ba.err, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+            for (uint32_t r : wb)
+                if (herr[r]) rest.push_back(r);
+        }
+        cls[1].swap(rest);
+    }
+    for (int c = 0; c < 2; c++) {
+        if (cls[c].empty()) continue;
+        HIP_CHECK(hipMemcpyAsync(d_lanes, cls[c].data(), sizeof(uint32_t) * cls[c].size(), hipMemcpyHostToDevice, s));
+        if (c == 0) hipLaunchKernelGGL((sparse_backward_kernel<64, false, true>), dim3((unsigned)cls[c].size()), dim3(64), 0, s, ba);
+        else hipLaunchKernelGGL((sparse_backward_kernel<KMAX, false, true>), dim3((unsigned)cls[c].size()), dim3(64), 0, s, ba);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));  // the lane list is reused by the next class
+    }
+    {
+        std::vector<uint32_t> herr(R);
+        HIP_CHECK(hipMemcpy(herr.data(), ba.err, sizeof(uint32_t) * R, hipMemcpyDeviceToHost));
+        for (uint64_t r = 0; r < R; r++)
+            if (herr[r]) PHMM_THROW(PHMM_EINTERNAL, "run_with_mapping state pass error " + std::to_string(herr[r]) + " (read " +
+                                                        std::to_string(r) + ")");
+    }
+    trace("state list pass");
+    if (stage_sl) copy_out(out_sl, d_sl.p, sizeof(double) * 3 * n_ent);
+    if (stage_best) copy_out(out_best, d_best.p, sizeof(uint32_t) * n_pos);
     put_doubles(out_lf, lf.data(), R);
 }
 

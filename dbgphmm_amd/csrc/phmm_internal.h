@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/phmm_amd.h"
+#include "../../include/phmm_amd_states.h"
 
 namespace phmm {
 
@@ -424,6 +425,8 @@ struct Knobs {
                                      // lists stays on the generic kernel (wide_bwd_kernel.h) -- the two halves apart, for tests
     bool wide_edge_bwd = false;      // PHMM_WIDE_EDGE_BWD: with PHMM_WIDE_HINTED, the backward half of run_with_mapping_edges on a block
                                      // as well (wide_backward_kernel<true, true>).  Opt-in of its own: DESIGN.md section 6
+    bool wide_states_bwd = false;    // PHMM_WIDE_STATES_BWD: with PHMM_WIDE_HINTED, the backward half of run_with_mapping_states on a block
+                                     // (wide_backward_kernel<true, false, BS, true>).  Opt-in of its own, as PHMM_WIDE_EDGE_BWD
     int wide_bwd_t = 0;              // PHMM_WIDE_BWD_T: threads of the list backward's block for reads with lists of at most 128 nodes,
                                      // 128 / 448 (anything else, 0: automatic -- 128 when there are more such reads than 448-thread
                                      // blocks the device holds at once, mapping_flow.hip)
@@ -491,6 +494,8 @@ void generate_mappings_hinted(phmm_model *m, const phmm_reads *reads, const phmm
 // run_with_mapping + to_edge_and_init_freqs over the reads (mapping_flow.hip)
 void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
                             double *out_ef, double *out_if);
+void run_with_mapping_states(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
+                             double *out_state_logp, uint32_t *out_best);
 struct MappingSink;
 // by_ratio: use_max_ratio of forward_sparse (forward.rs:93-154); false = fixed warm-up + top n_active_nodes
 void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_logp, double *out_total,

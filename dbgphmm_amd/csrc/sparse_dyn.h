@@ -161,7 +161,44 @@ struct SparseBwdEdgeArgs : SparseBwdArgs {
     double *rec_val;
     uint64_t *rec_cnt;        // [total_pos] slots used
 };
-template <bool EDGES> using SparseBwdArgsOf = typename std::conditional<EDGES, SparseBwdEdgeArgs, SparseBwdArgs>::type;
+// The state-posterior form of the list mode (sparse_backward_kernel<CAP, false, true>): instead of mapping lists, every
+// step writes PHMMOutput::to_emit_probs of its merged index by state (table.rs:500-505) over the entries of the INPUT
+// list of the position the index belongs to, and the head of its to_states() (table.rs:215-254).
+struct SparseBwdStatesArgs : SparseBwdArgs {
+    double *st_logp;    // [list entries][3] ln of Match, Ins, Del in the order of a.list_nodes, or null
+    uint32_t *st_best;  // [total_pos] (slot << 2) | kind of the largest value of the position, ST_NONE if none is finite; or null
+};
+static constexpr uint32_t ST_NONE = 0xffffffffu;
+template <bool EDGES, bool STATES = false>
+using SparseBwdArgsOf =
+    typename std::conditional<STATES, SparseBwdStatesArgs, typename std::conditional<EDGES, SparseBwdEdgeArgs, SparseBwdArgs>::type>::type;
+
+// The head of to_states() (table.rs:237-238: a stable ascending sort, then reversed): the largest value; among equal
+// values Del before Ins before Match, and within a kind the later slot.  An entry's rank is kind * ST_RANK + slot
+// (slot < 400), -1 = none yet; -inf never wins.
+static constexpr int ST_RANK = 512;
+__device__ __forceinline__ void st_take(double &bv, int &br, double v, int rank) {
+    if (v > bv || (v == bv && rank > br && v > -INFINITY)) {
+        bv = v;
+        br = rank;
+    }
+}
+// ... over the 64 lanes of a wave: every lane gets the head
+__device__ __forceinline__ void st_wave_best(double &bv, int &br) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ov = __shfl_xor(bv, off);
+        const int orr = __shfl_xor(br, off);
+        st_take(bv, br, ov, orr);
+    }
+}
+__device__ __forceinline__ uint32_t st_code(int rank) {
+    return rank < 0 ? ST_NONE : ((uint32_t)(rank % ST_RANK) << 2) | (uint32_t)(rank / ST_RANK);
+}
+// ln(f b 2^(E_f + E_b) / P) formed in logs, w = (E_f + E_b) ln 2 - ln P; a zero factor is -inf
+__device__ __forceinline__ double st_log(double f, double b, double w) {
+    return f > 0.0 && b > 0.0 ? log(f) + log(b) + w : -INFINITY;
+}
 
 // stop[gi] on exit: s0      -> finished (column s0+1 handed to the dense kernel)
 //                   len     -> nothing done (the record of the last position does not fit the class)

@@ -25,6 +25,10 @@
 //     one writes the edge and Begin terms of merged index pos (emit_edge_terms / emit_begin_terms, thread = slot) into
 //     the record of position pos.  A thread's terms go behind those of the threads before it (a block scan of the
 //     counts of non-zero terms): slot-major, child-minor, the order rec_append gives the one-wave kernel's chunks of 64.
+//   * wide_backward_kernel<true, false, BS, true>: the state-posterior form (sparse_backward_kernel<CAP, false, true>):
+//     the same columns, and in the place of the mapping list the three logs of to_emit_probs by state for every entry
+//     of the INPUT list of position pos-1, thread = slot of that list, plus the head of to_states() of the position: a
+//     wave reduction over (value, kind, slot) and one pair per wave through sh.red / sh.wsum (wb_states).  No sort.
 // The block has two sizes (BS): 448 threads for lists of up to 400 nodes, and, for the list flavours, 128 threads (two
 // waves, a third of the LDS) for reads whose longest list holds at most 128 nodes.  Both run the same per-slot
 // expressions, the same wave-0 sums (lane j adds the slots j, j + 64, ...), the same sorting network on the same padded
@@ -209,9 +213,76 @@ struct WideBwdListArgs : SparseBwdArgs {
 struct WideBwdEdgeArgs : SparseBwdEdgeArgs {
     unsigned long long *cells;
 };
-template <bool LIST, bool EDGES>
-using WideBwdArgsOf = typename std::conditional<LIST, typename std::conditional<EDGES, WideBwdEdgeArgs, WideBwdListArgs>::type,
-                                                SparseBwdArgs>::type;
+// ... and those of its state-posterior form
+struct WideBwdStatesArgs : SparseBwdStatesArgs {
+    unsigned long long *cells;
+};
+template <bool LIST, bool EDGES, bool STATES = false>
+using WideBwdArgsOf = typename std::conditional<
+    LIST,
+    typename std::conditional<STATES, WideBwdStatesArgs, typename std::conditional<EDGES, WideBwdEdgeArgs, WideBwdListArgs>::type>::type,
+    SparseBwdArgs>::type;
+
+// (STATES) to_emit_probs of one merged index by state over the entries of the input list of read position rq
+// (emit_states, mapping_flow.hip, thread = slot): sh.f* = F.tables[p] (fn entries, exponent fE), b = B.tables[p+1] with
+// exponent Eb (null: b_init, p_end in every state of every node, exponent 0).  A thread keeps its list entry in a
+// register and looks its node up in the record -- its own slot first, then the whole record -- and in b's hash.  The
+// head of to_states() is a wave reduction over (value, kind, slot) and, across the waves, thread 0's pass over one
+// pair per wave.  False: the list is longer than the block (the same for every thread).  Ends behind a barrier: the
+// next step loads another record into sh.f*.
+template <class Sh, class Col>
+__device__ __forceinline__ bool wb_states(const SparseBwdStatesArgs &a, uint64_t rq, Sh &sh, int &par, int fn, int fE, const Col *b,
+                                          int Eb, double logP, bool ok) {
+    const int t = threadIdx.x;
+    const uint64_t l0 = a.list_off[rq];
+    const int nl = (int)(a.list_off[rq + 1] - l0);
+    if (nl > Sh::CAP) return false;
+    double bv = -INFINITY;
+    int br = -1;
+    if (t < nl) {
+        const uint32_t v = a.list_nodes[l0 + t];
+        const double pend = sh.lp.p_end;
+        const double w = (double)(fE + Eb) * SP_LN2 - logP;
+        int j = t < fn && sh.fid[t] == v ? t : -1;
+        for (int q = 0; j < 0 && q < fn; q++)
+            if (sh.fid[q] == v) j = q;
+        double lm = -INFINITY, li = -INFINITY, ld = -INFINITY;
+        if (ok && j >= 0) {
+            double bm = pend, bi = pend, bd = pend;
+            if (b) {
+                const int bs = wb_find(*b, v);
+                bm = bs >= 0 ? b->m[bs] : 0.0;
+                bi = bs >= 0 ? b->i[bs] : 0.0;
+                bd = bs >= 0 ? b->d[bs] : 0.0;
+            }
+            lm = st_log(sh.fm[j], bm, w);
+            li = st_log(sh.fi[j], bi, w);
+            ld = st_log(sh.fd[j], bd, w);
+        }
+        if (a.st_logp) {
+            double *o = a.st_logp + 3 * (l0 + (uint64_t)t);
+            o[0] = lm;
+            o[1] = li;
+            o[2] = ld;
+        }
+        st_take(bv, br, lm, t);
+        st_take(bv, br, li, ST_RANK + t);
+        st_take(bv, br, ld, 2 * ST_RANK + t);
+    }
+    st_wave_best(bv, br);
+    if ((t & 63) == 0) {
+        sh.red[par][t >> 6] = bv;
+        sh.wsum[par][t >> 6] = br;
+    }
+    __syncthreads();
+    if (t == 0 && a.st_best) {
+#pragma unroll
+        for (int w = 1; w < Sh::WAVES; w++) st_take(bv, br, sh.red[par][w], sh.wsum[par][w]);
+        a.st_best[rq] = st_code(br);
+    }
+    par ^= 1;
+    return true;
+}
 
 // (EDGES) The edge terms of merged index i for the forward entry in slot j of sh.f* (emit_edge_terms, mapping_flow.hip,
 // thread = slot), one per child of the node in the CSR's order:
@@ -267,9 +338,10 @@ __device__ __forceinline__ int wb_edge_terms(const SparseBwdEdgeArgs &a, const S
 }
 
 // (LIST: 4 waves per SIMD -- 128 VGPRs -- let two blocks of 448 share a CU, as the adaptive flavour's 127 do unasked)
-template <bool LIST = false, bool EDGES = false, int BS = WBK_T>
-__global__ void __launch_bounds__(BS, LIST ? 4 : 1) wide_backward_kernel(const WideBwdArgsOf<LIST, EDGES> a) {
-    static_assert(LIST || (!EDGES && BS == WBK_T), "the adaptive flavour has one size and no edge terms");
+template <bool LIST = false, bool EDGES = false, int BS = WBK_T, bool STATES = false>
+__global__ void __launch_bounds__(BS, LIST ? 4 : 1) wide_backward_kernel(const WideBwdArgsOf<LIST, EDGES, STATES> a) {
+    static_assert(LIST || (!EDGES && !STATES && BS == WBK_T), "the adaptive flavour has one size, no edge terms and no state posteriors");
+    static_assert(!(EDGES && STATES), "one flavour at a time");
     static_assert(BS == WBK_T || BS == WBK_T_SMALL, "two block sizes");
     using Sh = WideBwdSharedT<BS>;
     using Col = WBColT<BS>;
@@ -319,6 +391,8 @@ __global__ void __launch_bounds__(BS, LIST ? 4 : 1) wide_backward_kernel(const W
                 if (cnt) wb_edge_terms<true>(a, sh, t, sh.col[0], true, sh.col[0], true, 0, 0.0, wD, base + (uint64_t)at);
                 end_fill = (uint64_t)tot;
             }
+        } else if constexpr (STATES) {
+            if (!wb_states<Sh, Col>(a, q0 + (uint64_t)(len - 1), sh, par, fn, fE, nullptr, 0, logP, ok)) err |= SP_ERR_CAPACITY;
         } else {
             const double w = ok ? exp((double)fE * SP_LN2 - logP) * lp.p_end : 0.0;
             if (t < fn) sh.dA[t] = w * (sh.fm[t] + sh.fi[t] + sh.fd[t]);
@@ -567,6 +641,11 @@ __global__ void __launch_bounds__(BS, LIST ? 4 : 1) wide_backward_kernel(const W
                 break;
             }
             if constexpr (EDGES) continue;  // no mapping list
+            if constexpr (STATES) {
+                // merged index pos >= 1 belongs to read position pos-1: sh.f* = F.tables[pos-1], cur = B.tables[pos]
+                if (!wb_states<Sh, Col>(a, q0 + (uint64_t)(pos - 1), sh, par, fn, fE, &cur, Ecur, logP, ok)) err |= SP_ERR_CAPACITY;
+                continue;  // no mapping list
+            }
         }
         // S = F.tables[pos-1] (.) B.tables[pos] / P over F's elements (table.rs:320-345, 500-505)
         const double w = ok ? exp((double)(fE + Ecur) * SP_LN2 - logP) : 0.0;

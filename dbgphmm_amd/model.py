@@ -284,6 +284,25 @@ class PHMMModel:
         _ffi.check(_ffi.lib().phmm_run_with_mapping_edges(self._h, reads._h, mappings._h, _ptr(lf), _ptr(ef), _ptr(nf)))
         return lf, ef[:self.n_edges], nf
 
+    def run_with_mapping_states(self, reads: ReadCollection, mappings: Mappings, want_states: bool = True,
+                                want_best: bool = True):
+        """PHMMModel::run_with_mapping (freq.rs:72-76) of every read on its lists, then per read position p
+        PHMMOutput::to_emit_probs(p + 1) by state (table.rs:500-505) over the entries of the input lists and the head
+        of its to_states() (table.rs:215-254)
+        -> (per-read ln P, state_logp[total_entries, 3] | None, best[total_bases] | None).
+        state_logp[a] = ln of Match, Ins, Del of entry a of the mappings' CSR (-inf: probability 0);
+        best[g] = (slot << 2) | kind (0 Match, 1 Ins, 2 Del) of the position's largest value -- among equal values Del
+        before Ins before Match, then the later slot --, 0xffffffff where no value is finite."""
+        L = _ffi.lib()
+        te = int(L.phmm_mappings_total_entries(mappings._h))
+        lf = np.empty(len(reads))
+        sl = np.empty((te, 3)) if want_states else None
+        best = np.empty(reads.total_bases(), dtype=np.uint32) if want_best else None
+        _ffi.check(L.phmm_run_with_mapping_states(self._h, reads._h, mappings._h, _ptr(lf),
+                                                  _ptr(sl) if want_states and te else None,
+                                                  _ptr(best) if want_best and best.size else None))
+        return lf, sl, best
+
     def q_score_exact(self, edge_freqs: np.ndarray, init_freqs: np.ndarray):
         """q_score_exact (src/hmmv2/q.rs:66-96) -> (init, trans, prior); QScore::total() is their sum."""
         ef = np.ascontiguousarray(edge_freqs, dtype=np.float64)

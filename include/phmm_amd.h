@@ -372,6 +372,10 @@ int phmm_generate_mappings(phmm_model *m, const phmm_reads *reads,
 int phmm_run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mappings,
                                 double *out_logp_forward, double *out_edge_freq, double *out_init_freq);
 
+/* The posterior by state over the lists (to_emit_probs per entry, the head of to_states() per base):
+ * phmm_amd_states.h, which includes this header.  This header's symbol table is closed: the ABI tests pin
+ * it, and entry points added since are declared in companion headers of their own. */
+
 /* ---- instrumentation ------------------------------------------------------------
  * Device time (ms, HIP events on the call's stream) and launch count of the dominant
  * kernel class in the most recent call of this thread, plus the algorithmic cell
@@ -391,6 +395,8 @@ int phmm_run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const ph
  * PHMM_WIDE_HINTED=1, phmm_run_with_mapping_edges runs its backward half on a block as
  * well and adds that half's launches and cells (list entries of the positions it
  * computed) to index 4; without that knob the call counts its forward half alone.
+ * phmm_run_with_mapping_states counts in the same way, its backward half with
+ * PHMM_WIDE_STATES_BWD=1 beside PHMM_WIDE_HINTED=1.
  * PHMM_WIDE_BWD_T=128 sends the reads of a block backward whose longest list holds at most
  * 128 nodes to a block of 128 threads (one more launch, the same cells, the same bits);
  * PHMM_WIDE_BWD_T=448 keeps every such read on the block of 448.  Unset, the library takes

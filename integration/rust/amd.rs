@@ -14,6 +14,7 @@ use super::amd_sys::*;
 use super::common::{PHMMEdge, PHMMModel, PHMMNode};
 use super::hint::{Mapping, Mappings};
 use super::params::PHMMParams;
+use super::sample::State;
 use crate::common::collection::ReadCollection;
 use crate::common::{CopyNum, Seq};
 use crate::multi_dbg::neighbors::UpdateInfo;
@@ -290,6 +291,47 @@ impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
         });
         ef.truncate(self.n_edges());
         (ef, nf)
+    }
+
+    /// run_with_mapping (freq.rs:72-76) of every read on its lists, then per read and read position p
+    /// `to_emit_probs(p + 1).to_states()` (table.rs:500-505, 215-254): the Match / Ins / Del states of the listed nodes
+    /// with their posteriors, most probable first (equal values in the reference's order: Del before Ins before Match,
+    /// the later list entry first).  Built on the host from the three planes of phmm_run_with_mapping_states.
+    /// Unverified, like the rest of this shim: it has not been compiled here.
+    pub fn to_states_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings) -> Vec<Vec<Vec<(State, Prob)>>> {
+        let m = AmdModel::new(self);
+        let mp = AmdMappings::from_mappings(reads, mappings);
+        let te = unsafe { phmm_mappings_total_entries(mp.0) } as usize;
+        let mut sl = vec![0f64; 3 * te.max(1)];
+        check(unsafe {
+            phmm_run_with_mapping_states(m.0, reads.h, mp.0, ptr::null_mut(), sl.as_mut_ptr(), ptr::null_mut())
+        });
+        let mut a = 0usize;  // entry of the CSR: the order from_mappings wrote
+        let mut out = Vec::with_capacity(mappings.n_reads());
+        for i in 0..mappings.n_reads() {
+            let mapping: &Mapping = &mappings[i];
+            let mut per_pos = Vec::with_capacity(mapping.len());
+            for j in 0..mapping.len() {
+                let nodes = &mapping.nodes[j];
+                let mut states: Vec<(State, Prob)> = Vec::with_capacity(3 * nodes.len());
+                for kind in 0..3 {
+                    for (slot, &v) in nodes.iter().enumerate() {
+                        let p = Prob::from_log_prob(sl[3 * (a + slot) + kind]);
+                        states.push(match kind {
+                            0 => (State::Match(v), p),
+                            1 => (State::Ins(v), p),
+                            _ => (State::Del(v), p),
+                        });
+                    }
+                }
+                states.sort_by_key(|(_, p)| *p);  // (stable, then reversed: table.rs:237-238)
+                states.reverse();
+                a += nodes.len();
+                per_pos.push(states);
+            }
+            out.push(per_pos);
+        }
+        out
     }
 
     /// q_score_exact (q.rs:66-96) from the transition posteriors over the lists -> (init, trans, prior)

@@ -161,6 +161,10 @@ extern "C" {
     pub fn phmm_run_with_mapping_edges(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
                                        out_logp_forward: *mut f64, out_edge_freq: *mut f64, out_init_freq: *mut f64)
                                        -> c_int;
+    // (include/phmm_amd_states.h, the companion header)
+    pub fn phmm_run_with_mapping_states(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                        out_logp_forward: *mut f64, out_state_logp: *mut f64, out_best: *mut u32)
+                                        -> c_int;
 
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
