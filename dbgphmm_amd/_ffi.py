@@ -101,6 +101,7 @@ def lib():
         "phmm_generate_mappings": (i32, [vp, vp, vp, i32, P(vp), vp]),
         "phmm_run_with_mapping_edges": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_run_with_mapping_states": (i32, [vp, vp, vp, vp, vp, vp]),
+        "phmm_run_with_mapping_best_path": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_last_call_stats": (i32, [i32, P(dbl), P(u64), P(u64)]),
         "phmm_enable_timing": (i32, [i32]),
     }
@@ -131,7 +132,8 @@ DECLARED_SYMBOLS = [
 
 # entry points declared in companion headers of include/phmm_amd.h (whose own symbol table, DECLARED_SYMBOLS, is closed):
 # header -> symbols.  lib() binds them with the rest.
-EXTENSION_SYMBOLS = {"phmm_amd_states.h": ["phmm_run_with_mapping_states"]}
+EXTENSION_SYMBOLS = {"phmm_amd_states.h": ["phmm_run_with_mapping_states"],
+                     "phmm_amd_path.h": ["phmm_run_with_mapping_best_path"]}
 
 
 def check(rc: int) -> None:

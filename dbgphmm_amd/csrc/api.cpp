@@ -1023,4 +1023,14 @@ int phmm_run_with_mapping_states(phmm_model *m, const phmm_reads *reads, const p
     });
 }
 
+int phmm_run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_logp,
+                                    uint32_t *out_path, uint32_t *out_counts) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        check_mapping_nodes(m, mp, reads);
+        if (reads->R == 0) return;
+        run_with_mapping_best_path(m, reads, mp, out_logp, out_path, out_counts);
+    });
+}
+
 }  // extern "C"

@@ -12,6 +12,7 @@
 
 #include "../../include/phmm_amd.h"
 #include "../../include/phmm_amd_states.h"
+#include "../../include/phmm_amd_path.h"
 
 namespace phmm {
 
@@ -496,6 +497,9 @@ void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_m
                             double *out_ef, double *out_if);
 void run_with_mapping_states(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
                              double *out_state_logp, uint32_t *out_best);
+// the best path of every read over its lists and its ln P (best_path.hip)
+void run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_logp,
+                                uint32_t *out_path, uint32_t *out_counts);
 struct MappingSink;
 // by_ratio: use_max_ratio of forward_sparse (forward.rs:93-154); false = fixed warm-up + top n_active_nodes
 void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_logp, double *out_total,

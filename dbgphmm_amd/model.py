@@ -158,6 +158,28 @@ class DenseTables:
         return self.scal[:, 2]
 
 
+PATH_NONE = 0xFFFFFFFF       # PHMM_PATH_NONE (include/phmm_amd_path.h)
+PATH_INS_BEGIN = 0xFFFFFFFD  # PHMM_PATH_INS_BEGIN
+
+
+def path_states(mappings: "Mappings", read: int, path: np.ndarray) -> List[Tuple[Optional[int], str]]:
+    """The rows of read `read` in the path of PHMMModel.run_with_mapping_best_path as the states the path passes, in
+    order: [(node, kind), ...] with kind 'M', 'I' or 'D' and node = nodes[pos_off[g] + slot] of the mappings' CSR, or
+    (None, 'IB') for InsBegin.  Empty for a read without a path."""
+    po, nd, _ = mappings.arrays()
+    g0, g1 = int(mappings.reads.offsets[read]), int(mappings.reads.offsets[read + 1])
+    out: List[Tuple[Optional[int], str]] = []
+    for g in range(g0, g1):
+        for code in path[g].tolist():
+            if code == PATH_NONE:
+                break
+            if code == PATH_INS_BEGIN:
+                out.append((None, "IB"))
+            else:
+                out.append((int(nd[int(po[g]) + (code >> 2)]), "MID"[code & 3]))
+    return out
+
+
 class PHMMModel:
     """PHMMModel<N, E> (src/hmmv2/common.rs:61-64) resident on one MI355X."""
 
@@ -302,6 +324,24 @@ class PHMMModel:
                                                   _ptr(sl) if want_states and te else None,
                                                   _ptr(best) if want_best and best.size else None))
         return lf, sl, best
+
+    def run_with_mapping_best_path(self, reads: ReadCollection, mappings: Mappings, want_path: bool = True):
+        """The best path (Viterbi) of every read over its lists: forward_with_mapping (forward.rs:51-75) with every sum
+        replaced by a maximum, and the walk back (include/phmm_amd_path.h)
+        -> (logp[R], path[total_bases, stride] | None, counts[R, 4]).
+        logp[r] = ln P of the best path (-inf: none); stride = n_max_gaps + 2; row g of path: entry 0 the emitting state
+        of the base, (slot << 2) | 0 Match / 1 Ins or PATH_INS_BEGIN, then the Del states behind it as (slot << 2) | 2,
+        then PATH_NONE; counts = matches, mismatches, insertions, deletions of the path.  path_states() turns the rows
+        of one read into (node, kind) pairs."""
+        R = len(reads)
+        stride = int(self.param.n_max_gaps) + 2
+        lp = np.empty(R)
+        counts = np.empty((R, 4), dtype=np.uint32)
+        path = np.empty((reads.total_bases(), stride), dtype=np.uint32) if want_path else None
+        _ffi.check(_ffi.lib().phmm_run_with_mapping_best_path(self._h, reads._h, mappings._h, _ptr(lp),
+                                                               _ptr(path) if want_path and path.size else None,
+                                                               _ptr(counts)))
+        return lp, path, counts
 
     def q_score_exact(self, edge_freqs: np.ndarray, init_freqs: np.ndarray):
         """q_score_exact (src/hmmv2/q.rs:66-96) -> (init, trans, prior); QScore::total() is their sum."""

@@ -334,6 +334,49 @@ impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
         out
     }
 
+    /// The best path (Viterbi) of every read over its lists: forward_with_mapping (forward.rs:51-75) with every sum
+    /// replaced by a maximum, and the walk back (phmm_run_with_mapping_best_path, include/phmm_amd_path.h).  Per read
+    /// the probability of the path and the states it passes in order, Del states included; (Prob::zero(), empty) for a
+    /// read without a path of positive probability on its lists.  The reference has no such call.
+    /// Unverified, like the rest of this shim: it has not been compiled here.
+    pub fn best_path_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings) -> Vec<(Prob, Vec<State>)> {
+        let m = AmdModel::new(self);
+        let mp = AmdMappings::from_mappings(reads, mappings);
+        let stride = self.param.n_max_gaps + 2;
+        let n_bases: usize = (0..mappings.n_reads()).map(|i| mappings[i].len()).sum();
+        let mut logp = vec![0f64; mappings.n_reads().max(1)];
+        let mut path = vec![PHMM_PATH_NONE; (stride * n_bases).max(1)];
+        check(unsafe {
+            phmm_run_with_mapping_best_path(m.0, reads.h, mp.0, logp.as_mut_ptr(), path.as_mut_ptr(), ptr::null_mut())
+        });
+        let mut g = 0usize;  // global base: the order from_mappings wrote
+        let mut out = Vec::with_capacity(mappings.n_reads());
+        for i in 0..mappings.n_reads() {
+            let mapping: &Mapping = &mappings[i];
+            let mut states = Vec::new();
+            for j in 0..mapping.len() {
+                for &code in &path[stride * g..stride * (g + 1)] {
+                    if code == PHMM_PATH_NONE {
+                        break;
+                    }
+                    states.push(if code == PHMM_PATH_INS_BEGIN {
+                        State::InsBegin
+                    } else {
+                        let v = mapping.nodes[j][(code >> 2) as usize];
+                        match code & 3 {
+                            0 => State::Match(v),
+                            1 => State::Ins(v),
+                            _ => State::Del(v),
+                        }
+                    });
+                }
+                g += 1;
+            }
+            out.push((Prob::from_log_prob(logp[i]), states));
+        }
+        out
+    }
+
     /// q_score_exact (q.rs:66-96) from the transition posteriors over the lists -> (init, trans, prior)
     pub fn q_score_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings) -> (f64, f64, f64) {
         let (ef, nf) = self.to_edge_and_init_freqs_with_mapping_amd(reads, mappings);

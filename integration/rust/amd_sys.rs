@@ -166,6 +166,13 @@ extern "C" {
                                         out_logp_forward: *mut f64, out_state_logp: *mut f64, out_best: *mut u32)
                                         -> c_int;
 
+    // (include/phmm_amd_path.h, the second companion header)
+    pub fn phmm_run_with_mapping_best_path(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                           out_logp: *mut f64, out_path: *mut u32, out_counts: *mut u32) -> c_int;
+
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
 }
+
+pub const PHMM_PATH_NONE: u32 = 0xffff_ffff;
+pub const PHMM_PATH_INS_BEGIN: u32 = 0xffff_fffd;
