@@ -57,7 +57,8 @@ extern "C" {
  *
  * Any output may be NULL, a host pointer or a device pointer; with out_path == NULL no path leaves the device.
  * Refusals are those of phmm_run_with_mapping_states, with nothing written: NULL model, reads or mappings and mappings
- * of another read set PHMM_EINVAL, a list of more than 400 nodes PHMM_ECAPACITY, node degree above 8 PHMM_EINVAL.  No
+ * of another read set PHMM_EINVAL, a list of more than 400 nodes PHMM_ECAPACITY, node degree above 8 PHMM_EINVAL.  A
+ * list that names a node >= the model's node count is PHMM_EINVAL too: the host checks the lists before any launch.  No
  * reads: nothing is written.  Repeated calls return the same bits, and a read's three outputs do not depend on which
  * other reads are in the call.  The back-pointers (16 bytes per list entry) come from the device workspace; under
  * phmm_set_workspace_limit the reads run in chunks.  Index 2 of phmm_last_call_stats counts the call's device time,
