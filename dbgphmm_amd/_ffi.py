@@ -103,6 +103,7 @@ def lib():
         "phmm_run_with_mapping_states": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_run_with_mapping_best_path": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_last_call_stats": (i32, [i32, P(dbl), P(u64), P(u64)]),
+        "phmm_last_call_prefix_share": (i32, [P(i32), P(u64)]),
         "phmm_enable_timing": (i32, [i32]),
     }
     for name, (res, args) in sig.items():
@@ -133,7 +134,8 @@ DECLARED_SYMBOLS = [
 # entry points declared in companion headers of include/phmm_amd.h (whose own symbol table, DECLARED_SYMBOLS, is closed):
 # header -> symbols.  lib() binds them with the rest.
 EXTENSION_SYMBOLS = {"phmm_amd_states.h": ["phmm_run_with_mapping_states"],
-                     "phmm_amd_path.h": ["phmm_run_with_mapping_best_path"]}
+                     "phmm_amd_path.h": ["phmm_run_with_mapping_best_path"],
+                     "phmm_amd_share.h": ["phmm_last_call_prefix_share"]}
 
 
 def check(rc: int) -> None:
@@ -146,3 +148,11 @@ def last_call_stats(which: int):
     ms, n, c = C.c_double(), C.c_uint64(), C.c_uint64()
     check(lib().phmm_last_call_stats(which, C.byref(ms), C.byref(n), C.byref(c)))
     return ms.value, n.value, c.value
+
+
+def last_call_prefix_share():
+    """(J, virtual lanes) of this thread's most recent adaptive call: the dense columns its reads shared by prefix
+    (0: off or declined) and the 4^J virtual reads walked for them (include/phmm_amd_share.h)."""
+    j, n = C.c_int(), C.c_uint64()
+    check(lib().phmm_last_call_prefix_share(C.byref(j), C.byref(n)))
+    return j.value, n.value

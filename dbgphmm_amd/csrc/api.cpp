@@ -38,7 +38,9 @@ void adopt_thread_context(const ThreadContext &c, hipStream_t stream, int workse
     g_stats = CallStats();
     workset_index() = workset;
 }
+static thread_local ShareInfo g_share;
 CallStats &stats() { return g_stats; }
+ShareInfo &share_info() { return g_share; }
 bool timing_enabled() { return g_timing; }
 
 uint64_t workspace_limit() {
@@ -94,6 +96,8 @@ void refresh_knobs() {
     k.dense_w = num("PHMM_DENSE_W", 0);
     k.dense_npt = num("PHMM_DENSE_NPT", 0);
     if (const char *e = std::getenv("PHMM_MEM_FRACTION")) k.mem_fraction = std::min(0.97, std::max(0.1, std::atof(e)));
+    k.share_prefix = num("PHMM_SHARE_PREFIX", -1);
+    if (k.share_prefix < 0 || k.share_prefix > 6) k.share_prefix = -1;
     g_knobs = k;
 }
 
@@ -339,6 +343,12 @@ int phmm_last_call_stats(int which, double *ms, uint64_t *launches, uint64_t *ce
     if (ms) *ms = g_stats.ms[which];
     if (launches) *launches = g_stats.launches[which];
     if (cells) *cells = g_stats.cells[which];
+    return PHMM_OK;
+}
+
+int phmm_last_call_prefix_share(int *out_columns, uint64_t *out_virtual_lanes) {
+    if (out_columns) *out_columns = g_share.J;
+    if (out_virtual_lanes) *out_virtual_lanes = g_share.J > 0 ? g_share.lanes : 0;
     return PHMM_OK;
 }
 

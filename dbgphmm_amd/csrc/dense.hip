@@ -32,6 +32,7 @@
 
 #include "dense_internal.h"
 #include "lds_dma.h"
+#include "prefix_share.h"
 
 #ifndef PHMM_FWD_PF
 #define PHMM_FWD_PF 2
@@ -531,8 +532,11 @@ __device__ __forceinline__ void bwd_chain(const DenseArgs &a, int g, int p, doub
 // j = L term F.tables[L-1] (.) B.init / P when pos == len-1).
 static constexpr int BDMA_DEPTH = 3;      // rows in flight per wave (5 planes = 2.5 KB per row)
 static constexpr int BDMA_SLOT = 5 * 64;  // doubles per slot: [B' m][B' i][F m][F i][F d]
-template <int W, bool DMA>
+// VF (prefix sharing, launches pos = 1 .. vJ - 1 of a sharing chunk): F of column pos-1 comes from the virtual plan's
+// tables, through a column base and a lane of its own per lane; everything else is the kernel as it stands.
+template <int W, bool DMA, bool VF = false>
 __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_step(const DenseArgs a, const int pos) {
+    static_assert(!VF || (W == 64 && !DMA), "the virtual-table loads go through the register ring of bwd_step<64>");
     __shared__ double lds[(BLOCK / 64) * 64];
     constexpr bool DMA_ = DMA && W == 64;
     __shared__ double ring[DMA_ ? (BLOCK / 64) * BDMA_DEPTH * BDMA_SLOT : 1];
@@ -654,6 +658,13 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
         fm = a.Fm + cprev; fi = a.Fi + cprev; fd = a.Fd + cprev;
         gm = a.Fm + ccur; gi = a.Fi + ccur; gd = a.Fd + ccur;
     }
+    int rf = r;  // the lane's column of the F rows
+    if (VF && want_post) {
+        const uint32_t v = share_lane_of_column(a.vlane[g * W + r], pos - 1);
+        const size_t vc = ((size_t)(v / SHARE_W) * a.vLc + (pos - 1)) * NW;
+        fm = a.vFm + vc; fi = a.vFi + vc; fd = a.vFd + vc;
+        rf = (int)(v % SHARE_W);
+    }
 
     double vmax = 0.0, s1 = 0.0, s2 = 0.0, pmx = 0.0, pmx2 = 0.0;
     double *Pa = a.want_map ? a.Pa + (size_t)g * NW : nullptr;
@@ -704,7 +715,7 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
             if (v0 > a.N - 1) v0 = a.N - 1;  // (a run past the end of the column: nothing is consumed)
             if (W == 64) v0 = __builtin_amdgcn_readfirstlane(v0);
             // (lanes that are not live read row 0 over and over: a cache hit instead of HBM traffic)
-            const size_t i0 = (size_t)(live ? v0 : 0) * W + r;
+            const size_t i0 = (size_t)(live ? v0 : 0) * W + r, i0f = (size_t)(live ? v0 : 0) * W + rf;
             nx_m[u] = nx_i[u] = nx_fm[u] = nx_fi[u] = nx_fd[u] = 0.0;
             if (DMA_) {
                 const uint32_t slot = ring_base + (uint32_t)u * (BDMA_SLOT * 8);
@@ -714,9 +725,9 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
             } else if (jtop >= 0) {
                 nx_m[u] = nm[i0];
                 nx_i[u] = ni[i0];
-                nx_fm[u] = lfm[i0];
-                nx_fi[u] = lfi[i0];
-                nx_fd[u] = lfd[i0];
+                nx_fm[u] = lfm[i0f];
+                nx_fi[u] = lfi[i0f];
+                nx_fd[u] = lfd[i0f];
             }
         }
         NodeRec nr_next{};
@@ -896,9 +907,9 @@ __global__ void __launch_bounds__(BLOCK, (W == 64 ? 4 : PHMM_SMALLW_WAVES)) bwd_
                         glds16(srcB + (size_t)vp * W, slot + 1024u);
                         if (l64 < 32) glds16(srcC + (size_t)vp * W, slot + 2048u);
                     } else {
-                        nx_fm[u] = lfm[(size_t)(live ? vp : 0) * W + r];
-                        nx_fi[u] = lfi[(size_t)(live ? vp : 0) * W + r];
-                        nx_fd[u] = lfd[(size_t)(live ? vp : 0) * W + r];
+                        nx_fm[u] = lfm[(size_t)(live ? vp : 0) * W + rf];
+                        nx_fi[u] = lfi[(size_t)(live ? vp : 0) * W + rf];
+                        nx_fd[u] = lfd[(size_t)(live ? vp : 0) * W + rf];
                     }
                 }
             }
@@ -1101,7 +1112,10 @@ template <int W> static void launch_bwd_one(const DenseArgs &a0, int pos, int g_
         g_cnt = a.ng;
         s = current_stream();
     }
-    if (W == 64 && dma)
+    if (W == 64 && a.vJ > 0 && pos >= 1 && pos <= a.vJ - 1)
+        // prefix sharing: F of column pos-1 lives in the virtual plan's tables (the LDS-DMA variant falls back to this one)
+        hipLaunchKernelGGL((bwd_step<W, false, W == 64>), dim3(a.nblk8, g_cnt), dim3(BLOCK), 0, s, a, pos);
+    else if (W == 64 && dma)
         hipLaunchKernelGGL((bwd_step<W, true>), dim3(a.nblk8, g_cnt), dim3(BLOCK), 0, s, a, pos);
     else
         hipLaunchKernelGGL((bwd_step<W, false>), dim3(a.nblk8, g_cnt), dim3(BLOCK), 0, s, a, pos);

@@ -79,6 +79,13 @@ struct DenseArgs {
     uint8_t *skA = nullptr;        // [2][ng][nrun] by column parity: bit s = segment s of the run was marked in that column
     int nrun = 0, nseg = 0, sseg = 1;
     unsigned long long *skcells = nullptr;  // live lanes x rows walked (the hulls of the marked segments; null: not counted)
+    // Prefix sharing ("Prefix sharing"; prefix_share.h, sparse_dyn.hip); vJ = 0: off.  The chunk's
+    // own tables hold m, i from column vJ - 1 on and d from there on too; columns 0 .. vJ - 2 exist only in the
+    // virtual plan's tables, where column j of lane (g, r) is lane vlane[g][r] mod 4^(j+1).  bwd_step<64> reads them
+    // there in its launches pos = 1 .. vJ - 1 (launch_bwd_step picks the instantiation).
+    const double *vFm = nullptr, *vFi = nullptr, *vFd = nullptr;  // [virtual groups][vLc][N][64]
+    const uint32_t *vlane = nullptr;                              // [ng][64] prefix index of the lane's read
+    int vLc = 0, vJ = 0;
 };
 static constexpr int WF_CAP = 1024;
 

@@ -13,6 +13,7 @@
 #include "../../include/phmm_amd.h"
 #include "../../include/phmm_amd_states.h"
 #include "../../include/phmm_amd_path.h"
+#include "../../include/phmm_amd_share.h"
 
 namespace phmm {
 
@@ -374,6 +375,13 @@ struct CallStats {
 };
 CallStats &stats();
 bool timing_enabled();
+// what the calling thread's last adaptive-sparse call shared by prefix (phmm_last_call_prefix_share): the columns J, 0 =
+// off or declined, and the virtual lanes 4^J
+struct ShareInfo {
+    int J = 0;
+    uint64_t lanes = 0;
+};
+ShareInfo &share_info();
 
 // Per-launch HIP-event timing of one kernel class on the call's stream (bench.py's roofline):
 // an event pair brackets every launch, the elapsed times are summed after one final sync.
@@ -450,6 +458,8 @@ struct Knobs {
     int dense_w = 0;                 // PHMM_DENSE_W
     int dense_npt = 0;               // PHMM_DENSE_NPT
     double mem_fraction = 0.0;       // PHMM_MEM_FRACTION (0: the defaults, 0.9 tables / 0.95 planned)
+    int share_prefix = -1;           // PHMM_SHARE_PREFIX: dense columns the reads of the main adaptive plan share by prefix
+                                     // (-1, unset: the planner's choice; 0: off; 1..6: that many, where the plan is eligible)
 };
 const Knobs &knobs();
 void refresh_knobs();

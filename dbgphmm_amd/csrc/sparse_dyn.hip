@@ -26,6 +26,7 @@
 #include <thread>
 
 #include "frontier_dev.h"
+#include "prefix_share.h"
 #include "sparse_dyn.h"
 #include "sparse_fwd_kernel.h"
 #include "wide_fwd_kernel.h"
@@ -222,6 +223,69 @@ __global__ void __launch_bounds__(BLOCK) warm_decide_fused(const WarmArgs wa, co
     }
 }
 
+// ---- prefix sharing ("Prefix sharing"; prefix_share.h) ---------------------------------------
+// The first J dense columns of every read of the main plan come from a virtual plan of 4^J reads, one per prefix,
+// computed once per call.  A chunk takes, before its launch J: the control values of columns 0 .. J-1 (share_copy_ctl)
+// and m, i of column J-1 (share_expand); columns 0 .. J-2 stay in the virtual tables, where bwd_step reads them.
+struct ShareArgs {
+    DenseArgs v;            // the virtual plan: [nvg][J][N][64] tables and their control arrays
+    DenseArgs d;            // the chunk
+    const uint32_t *vlane;  // [d.ng][64] prefix index of each lane's read (0: padding lanes)
+    int J;
+};
+__global__ void __launch_bounds__(BLOCK) share_copy_ctl(const ShareArgs sa, const int lanes) {
+    const int gi = blockIdx.x * BLOCK + threadIdx.x;
+    if (gi >= lanes || sa.d.len[gi] == 0) return;
+    const int g = gi / SHARE_W, r = gi % SHARE_W;
+    const uint32_t idx = sa.vlane[gi];
+    for (int j = 0; j < sa.J; j++) {
+        const uint32_t v = share_lane_of_column(idx, j);
+        const size_t vg = v / SHARE_W, vr = v % SHARE_W;
+        sa.d.FE[((size_t)g * (sa.d.Lc + 1) + j) * SHARE_W + r] = sa.v.FE[(vg * (sa.v.Lc + 1) + j) * SHARE_W + vr];
+        sa.d.cmaxF[((size_t)g * sa.d.Lc + j) * SHARE_W + r] = sa.v.cmaxF[(vg * sa.v.Lc + j) * SHARE_W + vr];
+        // (the totals maximum of column J-1 is made by the chunk's own launch J)
+        if (j + 1 < sa.J) sa.d.tmaxF[((size_t)g * sa.d.Lc + j) * SHARE_W + r] = sa.v.tmaxF[(vg * sa.v.Lc + j) * SHARE_W + vr];
+    }
+}
+// m, i of column J-1 for every lane of the chunk.  A block copies SHARE_ROWS nodes of one read group; the blocks of
+// ALL groups for one node range are dealt to one XCD one after the other (blocks b and b + 8 share an XCD), so a node
+// range of the virtual column is fetched from HBM once and served to the other groups by that XCD's L2.
+static constexpr int SHARE_ROWS = 32;
+__global__ void __launch_bounds__(BLOCK) share_expand(const ShareArgs sa, const int nrange) {
+    const unsigned b = blockIdx.x;
+    const unsigned t = b >> 3;
+    const int g = (int)(t % (unsigned)sa.d.ng);
+    const int c = (int)(t / (unsigned)sa.d.ng) * 8 + (int)(b & 7u);
+    if (c >= nrange) return;
+    const int r = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int gi = g * SHARE_W + r;
+    const bool on = sa.d.len[gi] != 0;
+    const uint32_t v = sa.vlane[gi];  // column J-1: the prefix index itself
+    const size_t NW = (size_t)sa.d.N * SHARE_W;
+    const size_t so = ((size_t)(v / SHARE_W) * sa.v.Lc + (sa.J - 1)) * NW + v % SHARE_W;
+    const size_t dof = ((size_t)g * sa.d.Lc + (sa.J - 1)) * NW + r;
+    const double *sm = sa.v.Fm + so, *si = sa.v.Fi + so;
+    double *dm = sa.d.Fm + dof, *di = sa.d.Fi + dof;
+    constexpr int PER = SHARE_ROWS / (BLOCK / 64);
+    double vm[PER], vi[PER];
+    const int k0 = c * SHARE_ROWS + w;
+#pragma unroll
+    for (int u = 0; u < PER; u++) {
+        const int k = k0 + u * (BLOCK / 64);
+        const bool ok = on && k < sa.d.N;
+        vm[u] = ok ? sm[(size_t)k * SHARE_W] : 0.0;
+        vi[u] = ok ? si[(size_t)k * SHARE_W] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < PER; u++) {
+        const int k = k0 + u * (BLOCK / 64);
+        if (on && k < sa.d.N) {
+            dm[(size_t)k * SHARE_W] = vm[u];
+            di[(size_t)k * SHARE_W] = vi[u];
+        }
+    }
+}
+
 // Forced switch (pos >= n_warmup) with more than 400 nodes inside the ratio: the reference's
 // `to_sorted_arrayvec()` keeps the 400 best of the dense nodevec (table.rs:139; ties resolved
 // by node index here).  One block per such read: compact the qualifying (node, total) pairs,
@@ -407,6 +471,9 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
     warm_cols = std::max<int64_t>(12, warm_cols);
     if (knobs().warm_cols > 0) warm_cols = std::max(4, knobs().warm_cols);
     const int chunk_groups = knobs().chunk_groups;  // 0: automatic
+    // the main plan (fixed mode: every read keeps all n_warmup dense columns, nothing is deferred)
+    std::unique_ptr<PlanCtx> main_pc(
+        new PlanCtx{make_plan(m, reads, 0), by_ratio ? warm_cols : (int64_t)prm.n_warmup + 2, by_ratio, {}});
     // Memory plan of the call, fixed HERE (nothing below reads the free-memory counter again).  The budget is a share
     // of free + pool-owned bytes (the pool's buffers are grow-only and reused: all of it is this call's to use).
     // Set aside first: what the buffers that do not scale with the read groups need for this read set -- forward
@@ -447,7 +514,76 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
         if (n_def > 64) lanes_def = (n_def + 63) / 64 * 64;
         limit_side = std::min<uint64_t>(limit_total / 8, lanes_def * per_read * 9 / 8);
     }
-    const uint64_t limit_main = limit_total - limit_side;
+    uint64_t limit_main = limit_total - limit_side;
+
+    // ---- prefix sharing: the planned J and the host side of its eligibility (prefix_share.h).
+    // Only the main adaptive plan at W = 64 shares; PHMM_SHARE_PREFIX: unset = the planner's J, 0 = off, 1..6 = that J.
+    // The virtual tables come out of the main plan's budget, at most 1 / SHARE_MEM_DIV of it.
+    struct ShareState {
+        int J = 0;
+        uint32_t nvl = 0;          // virtual lanes, 4^J
+        DenseArgs va{};            // the virtual plan
+        int digit_of[256];         // base code -> digit, -1: not a code the model emits
+        double ms = 0.0;
+        uint64_t launches = 0, cells = 0;
+    } share;
+    share_info() = ShareInfo();
+    std::vector<uint32_t> short_ids;  // reads too short to share, run in an unshared plan of their own (below)
+    if (by_ratio && main_pc->plan.W == SHARE_W && knobs().share_prefix != 0) {
+        const uint64_t cap = limit_main / SHARE_MEM_DIV;
+        const int forced = knobs().share_prefix;
+        int J = forced > 0 ? (share_table_bytes(forced, m->N) <= cap ? forced : 0)
+                           : share_choose_j(main_pc->plan.ng_total, m->N, cap);
+        // every read has J + 2 bases or more, the forced switch lies beyond launch J, and the first J bases of every
+        // read are among the (at most four) codes the model emits
+        if (J > 0 && (int64_t)J + 2 > prm.n_warmup) J = 0;
+        if (J > 0 && min_len < (uint64_t)J + 2) {
+            // A forced J takes the plan as it is: it declines.  The planner's own J may shape the plan first: a few
+            // reads of less than J + 2 bases (cfg3: 3 of 4 026, a walk that ended at a tip of the graph) leave the
+            // main plan for an unshared plan of their own, as the deferred reads do, and the rule then holds for
+            // every read of the plan; more than a fiftieth of the reads (8 at least) and the plan declines.
+            if (forced > 0) J = 0;
+            else {
+                for (uint64_t r = 0; r < R; r++)
+                    if (reads->off[r + 1] - reads->off[r] < (uint64_t)J + 2) short_ids.push_back((uint32_t)r);
+                if (short_ids.size() > std::max<uint64_t>(8, R / 50)) J = 0;
+                else {
+                    std::vector<uint32_t> long_ids;
+                    for (uint64_t r = 0; r < R; r++)
+                        if (reads->off[r + 1] - reads->off[r] >= (uint64_t)J + 2) long_ids.push_back((uint32_t)r);
+                    Plan lp = make_plan_ids(m, reads, long_ids);
+                    if (lp.W == SHARE_W) main_pc->plan = std::move(lp);
+                    else J = 0;
+                }
+                if (J == 0) short_ids.clear();
+            }
+        }
+        const auto in_main = [&](uint64_t r) { return short_ids.empty() || reads->off[r + 1] - reads->off[r] >= (uint64_t)J + 2; };
+        if (J > 0) {
+            std::fill(share.digit_of, share.digit_of + 256, -1);
+            bool seen[256] = {};
+            for (uint8_t e : m->emission) seen[e] = true;
+            int nc = 0;
+            for (int b = 0; b < 256; b++)
+                if (seen[b] && b != (int)'n') share.digit_of[b] = nc++;
+            if (nc > 4) J = 0;
+            for (uint64_t r = 0; r < R && J > 0; r++)
+                for (int i = 0; i < J && in_main(r); i++)
+                    if (share.digit_of[reads->bases[reads->off[r] + i]] < 0) {
+                        J = 0;
+                        break;
+                    }
+        }
+        if (J > 0) {
+            // tables + the control arrays of the virtual plan and of its exact counts (build_share)
+            const uint64_t vl = (uint64_t)share_groups(J) * SHARE_W;
+            const uint64_t bytes = share_table_bytes(J, m->N) + vl * ((uint64_t)PHMM_MAX_ACTIVE_NODES * 12 + 64 * (J + 1)) +
+                                   (uint64_t)share_groups(J) * m->N * 8 + ((uint64_t)4 << 20);
+            limit_main -= std::min(bytes, limit_main / 2);
+            share.J = J;
+            share.nvl = share_lanes(J);
+        }
+    }
 
     // cut a plan into items (caller holds `mu` or is the only thread)
     auto enqueue_plan = [&](std::unique_ptr<PlanCtx> pcu, std::deque<Item> &dst) {
@@ -556,6 +692,9 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
                      o_wnode = carve(sizeof(uint32_t) * (size_t)lanes * WF_CAP),
                      o_wtot = carve(sizeof(double) * (size_t)lanes * WF_CAP),
                      o_bases = carve((size_t)ngc * Lfull * W);
+        // prefix sharing: this chunk takes its first share.J columns from the virtual plan
+        const bool shared = share.J > 0 && it.pc->may_defer && by_ratio && W == SHARE_W;
+        const size_t o_vlane = carve(shared ? sizeof(uint32_t) * lanes : 0);
         warm.reserve(wb);
         char *wp = (char *)warm.p;
         HIP_CHECK(hipMemsetAsync(wp, 0, o_cnode, s));
@@ -597,6 +736,25 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
         }
         HIP_CHECK(hipMemcpyAsync((void *)a.len, hlc.data(), hlc.size() * sizeof(int), hipMemcpyHostToDevice, s));
         HIP_CHECK(hipMemcpyAsync((void *)a.logib, hib.data(), hib.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        std::vector<uint32_t> hvl(shared ? (size_t)lanes : 0, 0u);
+        if (shared) {
+            // the prefix index of every lane's read (padding lanes: 0, a lane that exists)
+            for (int gi = 0; gi < lanes; gi++) {
+                const size_t slot = (size_t)g0 * W + gi;
+                if (slot >= R) continue;
+                const uint8_t *rb = reads->bases.data() + reads->off[plan.order[slot]];
+                uint8_t dg[SHARE_MAX_J];
+                for (int i = 0; i < share.J; i++) dg[i] = (uint8_t)share.digit_of[rb[i]];
+                hvl[gi] = share_prefix_index(dg, share.J);
+            }
+            HIP_CHECK(hipMemcpyAsync(wp + o_vlane, hvl.data(), sizeof(uint32_t) * lanes, hipMemcpyHostToDevice, s));
+            a.vFm = share.va.Fm;
+            a.vFi = share.va.Fi;
+            a.vFd = share.va.Fd;
+            a.vlane = (const uint32_t *)(wp + o_vlane);
+            a.vLc = share.va.Lc;
+            a.vJ = share.J;
+        }
         HIP_CHECK(hipStreamSynchronize(s));
 
         WarmArgs wa{};
@@ -633,6 +791,17 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
         // (plans of deferred reads are a handful of lanes: they neither take nor wait for the token)
         const bool use_token = it.pc->may_defer || !by_ratio;
         if (use_token) dense_lock.lock();
+        if (shared) {
+            // columns 0 .. J-1 are the virtual plan's: their control values, and m, i of column J-1 for launch J
+            ShareArgs sa{share.va, a, a.vlane, share.J};
+            const int nrange = (int)((m->N + SHARE_ROWS - 1) / SHARE_ROWS), nrange8 = (nrange + 7) / 8 * 8;
+            lt.begin();
+            hipLaunchKernelGGL(share_copy_ctl, dim3((lanes + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, sa, lanes);
+            hipLaunchKernelGGL(share_expand, dim3((unsigned)nrange8 * (unsigned)ngc), dim3(BLOCK), 0, s, sa, nrange);
+            lt.end();
+            HIP_CHECK(hipGetLastError());
+            pos = share.J;
+        }
         if (!by_ratio) {
             // not adaptive (forward.rs:134-137): the first n_warmup tables are dense for every read; launch
             // min(n_warmup, Lc) completes column n_warmup-1 (its Del values) or ends the short reads
@@ -722,7 +891,8 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
         std::vector<uint32_t> sparse_lanes, need400;
         for (int gi = 0; gi < lanes; gi++) {
             if (hl[gi] == 0) continue;
-            dense_cells += (uint64_t)std::min(hsw[gi] + 1, hl[gi]) * m->N;
+            // (prefix sharing: the launches 0 .. J-1 of these lanes were never made; the virtual plan's cells are added once per call)
+            dense_cells += (uint64_t)(std::min(hsw[gi] + 1, hl[gi]) - (shared ? share.J : 0)) * m->N;
             if (hsw[gi] < hl[gi]) {
                 // ratio mode: a forced switch with more than 400 nodes inside the ratio; fixed mode: always
                 // (top_nodes(n_active_nodes) of the last dense column)
@@ -1027,16 +1197,126 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
         }
     };
 
+    // The virtual plan of the prefix sharing: 4^J reads of J + 1 bases, lane v holding digit i of v as its base i,
+    // laid out and walked like any chunk at W = 64 with the main plan's run length (launches 0 .. J-1, no switch
+    // bookkeeping).  Then the exact counts of its columns 0 .. J-2: a virtual lane that would have left the warm-up
+    // at a position <= J-1 makes the plan decline (share.J = 0).  The count of column J-1 is each chunk's launch J's.
+    auto build_share = [&](const Plan &mplan) {
+        hipStream_t s = current_stream();
+        const int J = share.J;
+        const int nvg = (int)share_groups(J), vl = nvg * SHARE_W;
+        DevBuf &vtab = m->pool->wsets[0].aux[22], &vmisc = m->pool->wsets[0].aux[23];
+        DenseArgs va{};
+        fill_model_args(va, m);
+        va.nblk = mplan.nblk;
+        va.nblk8 = mplan.nblk8;
+        va.npt = mplan.npt;
+        va.ng = nvg;
+        va.Lc = J;
+        size_t tb = 0, mb = 0;
+        layout(va, SHARE_W, false, nullptr, nullptr, tb, mb);
+        // (only the forward tables are used: the backward planes layout() puts behind them are never touched)
+        vtab.reserve((size_t)share_table_bytes(J, m->N) + 1024);
+        size_t cb = (mb + 255) / 256 * 256;
+        auto carve = [&](size_t bytes) {
+            cb = (cb + 255) / 256 * 256;
+            const size_t o = cb;
+            cb += bytes;
+            return o;
+        };
+        const size_t o_sw = carve(sizeof(int) * vl), o_cnt = carve(sizeof(int) * vl), o_cn = carve(sizeof(int) * vl),
+                     o_und = carve(sizeof(int) * 2), o_amb = carve(sizeof(int) * vl),
+                     o_cnode = carve(sizeof(uint32_t) * (size_t)vl * PHMM_MAX_ACTIVE_NODES),
+                     o_ctot = carve(sizeof(double) * (size_t)vl * PHMM_MAX_ACTIVE_NODES);
+        vmisc.reserve(cb);
+        layout(va, SHARE_W, false, vtab.p, vmisc.p, tb, mb);
+        char *cp = (char *)vmisc.p;
+        HIP_CHECK(hipMemsetAsync(cp, 0, o_cnode, s));
+        HIP_CHECK(hipMemsetAsync(cp + o_sw, 0xff, sizeof(int) * vl, s));   // sw = -1
+        HIP_CHECK(hipMemsetAsync(cp + o_amb, 0x01, sizeof(int) * vl, s));  // every lane takes the exact count
+        // bases [group][pos][64]; a digit the model has no code for (fewer than four codes) matches no node
+        uint8_t code_of[4] = {0xfe, 0xfe, 0xfe, 0xfe};
+        for (int b = 0; b < 256; b++)
+            if (share.digit_of[b] >= 0) code_of[share.digit_of[b]] = (uint8_t)b;
+        std::vector<uint8_t> hb((size_t)nvg * J * SHARE_W, 0xff);
+        std::vector<int> hlen((size_t)vl, 0);
+        for (uint32_t v = 0; v < share.nvl; v++) {
+            hlen[v] = J;  // (J + 1 bases, clamped to the J kept columns as a chunk clamps its reads)
+            for (int i = 0; i < J; i++) hb[((size_t)(v / SHARE_W) * J + i) * SHARE_W + v % SHARE_W] = code_of[share_digit(v, i)];
+        }
+        std::vector<double> hib;
+        host_logib(m, (size_t)J, hib);
+        HIP_CHECK(hipMemcpyAsync((void *)va.bases, hb.data(), hb.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync((void *)va.len, hlen.data(), hlen.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync((void *)va.logib, hib.data(), hib.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        LaunchTimer lt(timing_enabled());
+        for (int pos = 0; pos < J; pos++) {
+            lt.begin();
+            launch_fwd_step(SHARE_W, va, pos);
+            lt.end();
+        }
+        WarmArgs vwa{};
+        vwa.d = va;
+        vwa.sw = (int *)(cp + o_sw);
+        vwa.cnt = (int *)(cp + o_cnt);
+        vwa.cand_n = (int *)(cp + o_cn);
+        vwa.undecided = (int *)(cp + o_und);
+        vwa.n_amb = vwa.undecided + 1;
+        vwa.amb = (int *)(cp + o_amb);
+        vwa.cand_node = (uint32_t *)(cp + o_cnode);
+        vwa.cand_tot = (double *)(cp + o_ctot);
+        vwa.ratio_lin = std::exp(-prm.active_node_max_ratio);
+        vwa.n_warmup = (int)prm.n_warmup;
+        vwa.threshold = (int)prm.warmup_threshold;
+        for (int col = 0; col + 1 < J; col++) {
+            launch_col_count_w(SHARE_W, vwa, col);
+            hipLaunchKernelGGL(warm_decide, dim3((vl + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, vwa, col + 1, vl);
+        }
+        HIP_CHECK(hipGetLastError());
+        std::vector<int> hsw((size_t)vl, -1);
+        HIP_CHECK(hipMemcpyAsync(hsw.data(), vwa.sw, sizeof(int) * vl, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        share.ms = lt.total_ms();
+        share.launches = (uint64_t)J;
+        share.cells = (uint64_t)share.nvl * (uint64_t)J * m->N;
+        share.va = va;
+        for (uint32_t v = 0; v < share.nvl; v++)
+            if (hsw[v] >= 0) {
+                if (knobs().trace) std::fprintf(stderr, "      prefix sharing declined: virtual lane %u leaves the warm-up at position %d\n", v, hsw[v]);
+                share.J = 0;
+                break;
+            }
+        trace("prefix sharing: virtual plan");
+    };
+
     {
-        // fixed mode: every read keeps all n_warmup dense columns, nothing is deferred
-        std::unique_ptr<PlanCtx> pc(
-            new PlanCtx{make_plan(m, reads, 0), by_ratio ? warm_cols : (int64_t)prm.n_warmup + 2, by_ratio, {}});
         // few groups: one worker (the calling thread, on the caller's stream)
         const int min_groups = knobs().pipeline_min_groups;
-        if (pc->plan.ng_total < min_groups) n_workers = 1;
-        enqueue_plan(std::move(pc), queue);
+        if (main_pc->plan.ng_total < min_groups) n_workers = 1;
+        const Plan &mplan = main_pc->plan;
+        enqueue_plan(std::move(main_pc), queue);
+        // prefix sharing: every chunk keeps launch J and the column it speculates on; then the virtual plan, before
+        // any chunk runs.  A plan that declines runs as if sharing were off.
+        for (const Item &it : queue)
+            if (share.J + 2 > it.Lc) share.J = 0;
+        if (share.J > 0) build_share(mplan);
+        if (share.J > 0) share_info() = ShareInfo{share.J, (uint64_t)share.nvl};
     }
     const int n_threads = (int)std::min<size_t>((size_t)n_workers, queue.size());
+    if (!short_ids.empty()) {
+        // the reads the sharing plan left out: all their columns, unshared, beside the main plan where that is possible
+        // (the route of the deferred reads), else behind it
+        std::unique_ptr<PlanCtx> pc(new PlanCtx{make_plan_ids(m, reads, short_ids), (int64_t)prm.n_warmup + 2, false, {}});
+        const size_t side_group = ((size_t)(prm.n_warmup + 2) * 24 + 4 * 8 + (size_t)map_planes * 8) * m->N * pc->plan.W;
+        std::lock_guard<std::mutex> lk(mu);
+        if (n_threads <= 1 && side_on && side_group <= limit_side) {
+            enqueue_plan(std::move(pc), side_queue);
+            side_started = true;
+            start_side_worker();
+        } else {
+            enqueue_plan(std::move(pc), queue);
+        }
+    }
     if (n_threads <= 1) {
         single_mode = true;
         worker_loop();
@@ -1088,6 +1368,13 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
         stats() = merged;
     }
     if (first_error) std::rethrow_exception(first_error);
+    {
+        // the virtual plan of the prefix sharing (also when the plan declined after it was walked)
+        CallStats &st = stats();
+        st.ms[0] += share.ms;
+        st.launches[0] += share.launches;
+        st.cells[0] += share.cells;
+    }
     if (by_ratio) {
         reads->warm_hint = new_hint;
         reads->last_flags = new_flags;

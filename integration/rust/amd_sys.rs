@@ -172,6 +172,8 @@ extern "C" {
 
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
+    // (include/phmm_amd_share.h, the third companion header)
+    pub fn phmm_last_call_prefix_share(out_columns: *mut c_int, out_virtual_lanes: *mut u64) -> c_int;
 }
 
 pub const PHMM_PATH_NONE: u32 = 0xffff_ffff;
