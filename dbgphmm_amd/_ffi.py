@@ -102,6 +102,7 @@ def lib():
         "phmm_run_with_mapping_edges": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_run_with_mapping_states": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_run_with_mapping_best_path": (i32, [vp, vp, vp, vp, vp, vp]),
+        "phmm_run_with_mapping_sample_paths": (i32, [vp, vp, vp, u32, u64, vp, vp, vp, vp, vp]),
         "phmm_last_call_stats": (i32, [i32, P(dbl), P(u64), P(u64)]),
         "phmm_last_call_prefix_share": (i32, [P(i32), P(u64)]),
         "phmm_enable_timing": (i32, [i32]),
@@ -135,7 +136,8 @@ DECLARED_SYMBOLS = [
 # header -> symbols.  lib() binds them with the rest.
 EXTENSION_SYMBOLS = {"phmm_amd_states.h": ["phmm_run_with_mapping_states"],
                      "phmm_amd_path.h": ["phmm_run_with_mapping_best_path"],
-                     "phmm_amd_share.h": ["phmm_last_call_prefix_share"]}
+                     "phmm_amd_share.h": ["phmm_last_call_prefix_share"],
+                     "phmm_amd_sample.h": ["phmm_run_with_mapping_sample_paths"]}
 
 
 def check(rc: int) -> None:

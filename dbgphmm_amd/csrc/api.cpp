@@ -1043,4 +1043,17 @@ int phmm_run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, cons
     });
 }
 
+int phmm_run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
+                                       uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_path,
+                                       uint32_t *out_counts, uint32_t *out_node_usage) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        if (n_samples == 0 || n_samples > (uint32_t)PHMM_SAMPLE_MAX) PHMM_THROW(PHMM_EINVAL, "n_samples must be 1..64");
+        check_mapping_nodes(m, mp, reads);
+        if (reads->R == 0) return;
+        run_with_mapping_sample_paths(m, reads, mp, n_samples, seed, out_logp, out_path_logp, out_path, out_counts,
+                                      out_node_usage);
+    });
+}
+
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include "../../include/phmm_amd_states.h"
 #include "../../include/phmm_amd_path.h"
 #include "../../include/phmm_amd_share.h"
+#include "../../include/phmm_amd_sample.h"
 
 namespace phmm {
 
@@ -510,6 +511,10 @@ void run_with_mapping_states(phmm_model *m, const phmm_reads *reads, const phmm_
 // the best path of every read over its lists and its ln P (best_path.hip)
 void run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_logp,
                                 uint32_t *out_path, uint32_t *out_counts);
+// n_samples draws from the posterior over paths of every read over its lists (sample_paths.hip)
+void run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
+                                   uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_path,
+                                   uint32_t *out_counts, uint32_t *out_node_usage);
 struct MappingSink;
 // by_ratio: use_max_ratio of forward_sparse (forward.rs:93-154); false = fixed warm-up + top n_active_nodes
 void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_logp, double *out_total,

@@ -343,6 +343,30 @@ class PHMMModel:
                                                                _ptr(counts)))
         return lp, path, counts
 
+    def run_with_mapping_sample_paths(self, reads: ReadCollection, mappings: Mappings, n_samples: int, seed: int,
+                                      want_path: bool = True, want_usage: bool = False):
+        """n_samples (1..64) draws from the posterior over paths of every read over its lists, P(path | read, model,
+        lists): the forward sums as the filter and one random walk back per sample (include/phmm_amd_sample.h, which
+        writes out the sums, the random stream and the draw rule)
+        -> (logp[R], path_logp[R, S], path[S, total_bases, stride] | None, counts[R, S, 4], usage[S, n_nodes] | None).
+        logp[r] = ln Z, the forward total of the read over its lists as sets (-inf: no path); path_logp = ln P of each
+        sampled path; plane s of path is sample s of every read in the rows of run_with_mapping_best_path, so
+        path_states(mappings, read, path[s]) works on it; counts = matches, mismatches, insertions, deletions of each
+        sample; usage[s, v] = the Match, Ins and Del states of all reads on node v in sample s, one draw of what the
+        node frequencies are the expectation of.  A read's samples depend on seed, its index and s alone."""
+        R, S = len(reads), int(n_samples)
+        stride = int(self.param.n_max_gaps) + 2
+        lp = np.empty(R)
+        plp = np.empty((R, max(S, 0)))
+        counts = np.empty((R, max(S, 0), 4), dtype=np.uint32)
+        path = np.empty((max(S, 0), reads.total_bases(), stride), dtype=np.uint32) if want_path else None
+        usage = np.empty((max(S, 0), self.n_nodes), dtype=np.uint32) if want_usage else None
+        _ffi.check(_ffi.lib().phmm_run_with_mapping_sample_paths(
+            self._h, reads._h, mappings._h, S, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(lp), _ptr(plp) if plp.size else None,
+            _ptr(path) if want_path and path.size else None, _ptr(counts) if counts.size else None,
+            _ptr(usage) if want_usage and usage.size else None))
+        return lp, plp, path, counts, usage
+
     def q_score_exact(self, edge_freqs: np.ndarray, init_freqs: np.ndarray):
         """q_score_exact (src/hmmv2/q.rs:66-96) -> (init, trans, prior); QScore::total() is their sum."""
         ef = np.ascontiguousarray(edge_freqs, dtype=np.float64)

@@ -377,6 +377,59 @@ impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
         out
     }
 
+    /// n_samples (1..=64) draws from the posterior over paths of every read over its lists
+    /// (phmm_run_with_mapping_sample_paths, include/phmm_amd_sample.h): the forward sums as the filter and one random
+    /// walk back per sample.  Per read the forward total over its lists and, per sample, the probability of the sampled
+    /// path and the states it passes in order, Del states included; (Prob::zero(), empty) for a read without a path.
+    /// A read's samples depend on seed, its index and the sample number alone.  The reference has no such call.
+    /// Unverified, like the rest of this shim: it has not been compiled here.
+    pub fn sample_paths_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings, n_samples: usize, seed: u64)
+                                         -> Vec<(Prob, Vec<(Prob, Vec<State>)>)> {
+        let m = AmdModel::new(self);
+        let mp = AmdMappings::from_mappings(reads, mappings);
+        let stride = self.param.n_max_gaps + 2;
+        let n_reads = mappings.n_reads();
+        let n_bases: usize = (0..n_reads).map(|i| mappings[i].len()).sum();
+        let mut logp = vec![0f64; n_reads.max(1)];
+        let mut path_logp = vec![0f64; (n_reads * n_samples).max(1)];
+        let mut path = vec![PHMM_PATH_NONE; (n_samples * stride * n_bases).max(1)];
+        check(unsafe {
+            phmm_run_with_mapping_sample_paths(m.0, reads.h, mp.0, n_samples as u32, seed, logp.as_mut_ptr(),
+                                               path_logp.as_mut_ptr(), path.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())
+        });
+        let mut g0 = 0usize;  // first global base of the read: the order from_mappings wrote
+        let mut out = Vec::with_capacity(n_reads);
+        for i in 0..n_reads {
+            let mapping: &Mapping = &mappings[i];
+            let mut samples = Vec::with_capacity(n_samples);
+            for s in 0..n_samples {
+                let plane = &path[s * stride * n_bases..(s + 1) * stride * n_bases];
+                let mut states = Vec::new();
+                for j in 0..mapping.len() {
+                    for &code in &plane[stride * (g0 + j)..stride * (g0 + j + 1)] {
+                        if code == PHMM_PATH_NONE {
+                            break;
+                        }
+                        states.push(if code == PHMM_PATH_INS_BEGIN {
+                            State::InsBegin
+                        } else {
+                            let v = mapping.nodes[j][(code >> 2) as usize];
+                            match code & 3 {
+                                0 => State::Match(v),
+                                1 => State::Ins(v),
+                                _ => State::Del(v),
+                            }
+                        });
+                    }
+                }
+                samples.push((Prob::from_log_prob(path_logp[i * n_samples + s]), states));
+            }
+            g0 += mapping.len();
+            out.push((Prob::from_log_prob(logp[i]), samples));
+        }
+        out
+    }
+
     /// q_score_exact (q.rs:66-96) from the transition posteriors over the lists -> (init, trans, prior)
     pub fn q_score_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings) -> (f64, f64, f64) {
         let (ef, nf) = self.to_edge_and_init_freqs_with_mapping_amd(reads, mappings);

@@ -170,6 +170,11 @@ extern "C" {
     pub fn phmm_run_with_mapping_best_path(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
                                            out_logp: *mut f64, out_path: *mut u32, out_counts: *mut u32) -> c_int;
 
+    // (include/phmm_amd_sample.h, the fourth companion header)
+    pub fn phmm_run_with_mapping_sample_paths(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                              n_samples: u32, seed: u64, out_logp: *mut f64, out_path_logp: *mut f64,
+                                              out_path: *mut u32, out_counts: *mut u32, out_node_usage: *mut u32) -> c_int;
+
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
     // (include/phmm_amd_share.h, the third companion header)
