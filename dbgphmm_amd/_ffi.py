@@ -103,6 +103,7 @@ def lib():
         "phmm_run_with_mapping_states": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_run_with_mapping_best_path": (i32, [vp, vp, vp, vp, vp, vp]),
         "phmm_run_with_mapping_sample_paths": (i32, [vp, vp, vp, u32, u64, vp, vp, vp, vp, vp]),
+        "phmm_sample_reads": (i32, [vp, u64, u64, u32, u32, vp, u64, u64, vp, vp, vp, vp, u32, vp, vp]),
         "phmm_last_call_stats": (i32, [i32, P(dbl), P(u64), P(u64)]),
         "phmm_last_call_prefix_share": (i32, [P(i32), P(u64)]),
         "phmm_enable_timing": (i32, [i32]),
@@ -137,7 +138,8 @@ DECLARED_SYMBOLS = [
 EXTENSION_SYMBOLS = {"phmm_amd_states.h": ["phmm_run_with_mapping_states"],
                      "phmm_amd_path.h": ["phmm_run_with_mapping_best_path"],
                      "phmm_amd_share.h": ["phmm_last_call_prefix_share"],
-                     "phmm_amd_sample.h": ["phmm_run_with_mapping_sample_paths"]}
+                     "phmm_amd_sample.h": ["phmm_run_with_mapping_sample_paths"],
+                     "phmm_amd_generate.h": ["phmm_sample_reads"]}
 
 
 def check(rc: int) -> None:

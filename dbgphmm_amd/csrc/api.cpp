@@ -1056,4 +1056,27 @@ int phmm_run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, c
     });
 }
 
+int phmm_sample_reads(phmm_model *m, uint64_t first_index, uint64_t n_walks, uint32_t length, uint32_t length_kind,
+                      const uint32_t *start_nodes, uint64_t n_start_nodes, uint64_t seed, uint8_t *out_bases,
+                      uint32_t *out_len, uint32_t *out_flags, uint32_t *out_history, uint32_t history_cap,
+                      uint32_t *out_history_len, uint32_t *out_node_usage) {
+    return guarded_on(m, [&] {
+        if (length == 0 || length >= (1u << 28)) PHMM_THROW(PHMM_EINVAL, "length must be 1 .. 2^28 - 1");
+        if (length_kind > PHMM_GEN_EMIT_COUNT) PHMM_THROW(PHMM_EINVAL, "length_kind is none of PHMM_GEN_STATE_COUNT / ENDABLE / EMIT_COUNT");
+        if (n_start_nodes && !start_nodes) PHMM_THROW(PHMM_EINVAL, "start_nodes is NULL");
+        if (n_start_nodes >> 32) PHMM_THROW(PHMM_EINVAL, "more than 2^32 - 1 start nodes");
+        bool any = n_start_nodes == 0;
+        for (uint64_t j = 0; j < n_start_nodes; j++) {
+            if (start_nodes[j] >= m->N) PHMM_THROW(PHMM_EINVAL, "start node out of range");
+            any = any || m->init_logp[start_nodes[j]] > -INFINITY;
+        }
+        if (!any) PHMM_THROW(PHMM_EINVAL, "no start node has init > -inf (the reference panics: froms are empty)");
+        if (out_history && history_cap == 0) PHMM_THROW(PHMM_EINVAL, "out_history with history_cap == 0");
+        if (out_history && m->N > (1u << 30)) PHMM_THROW(PHMM_EINVAL, "history words hold node ids below 2^30");
+        if (n_walks == 0) return;
+        sample_reads(m, first_index, n_walks, length, length_kind, start_nodes, n_start_nodes, seed, out_bases, out_len,
+                     out_flags, out_history, history_cap, out_history_len, out_node_usage);
+    });
+}
+
 }  // extern "C"

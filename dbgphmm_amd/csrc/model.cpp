@@ -299,6 +299,7 @@ void model_upload(phmm_model *m) {
     for (uint32_t v = 0; v < N; v++)
         d.max_degree = std::max(d.max_degree, std::max(m->par_off[v + 1] - m->par_off[v], m->chi_off[v + 1] - m->chi_off[v]));
     d.logib_len = 0;  // parameters may have changed
+    m->gen_valid = false;  // so may init and trans: the sums of phmm_sample_reads are rebuilt on its next call
     // the host vectors above die at scope exit: make sure the async copies are done
     HIP_CHECK(hipStreamSynchronize(current_stream()));
 }

@@ -15,6 +15,7 @@
 #include "../../include/phmm_amd_path.h"
 #include "../../include/phmm_amd_share.h"
 #include "../../include/phmm_amd_sample.h"
+#include "../../include/phmm_amd_generate.h"
 
 namespace phmm {
 
@@ -259,6 +260,8 @@ struct ModelDev {
     DevBuf logib;                     // f64[logib_len] forward InsBegin chain (log)
     size_t logib_len = 0;
     uint32_t max_degree = 0;
+    DevBuf gen_rec, gen_child_c, gen_init_c;  // sample_reads.hip: a 64-byte record of every node's child pick [N], the running
+                                      // sums of the picks f64[E] and of the init pick f64[N]
 };
 
 // Successors for one segment length (run_succ.h with the segment as its run; seg_hull.h), on the device: what
@@ -282,6 +285,10 @@ struct phmm_model {
     std::vector<uint32_t> par_off, par_node, par_edge, chi_off, chi_node, chi_edge;
     std::vector<double> logib;  // forward InsBegin chain, log domain (forward.rs:541-545)
     phmm::ModelDev dev;
+    // what phmm_sample_reads reads beside the CSR (dev.gen_*): built on its first call, dropped by model_upload
+    bool gen_valid = false;
+    double gen_init_total = 0.0;
+    uint32_t gen_init_last = 0;
     double wf_ub_a = 0.0, wf_ub_b = 0.0;  // column total <= ub_a * max(m,i) + ub_b * p_ID * ib (model.cpp)
     // nodes of the descendant hop entries (bh) per node, kept on the host for the segment successors, and the
     // successors built so far, by segment length (the plans of one model use few); model_upload drops them
@@ -515,6 +522,11 @@ void run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, const ph
 void run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
                                    uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_path,
                                    uint32_t *out_counts, uint32_t *out_node_usage);
+// reads drawn from the model, one walk per lane (sample_reads.hip)
+void sample_reads(phmm_model *m, uint64_t first_index, uint64_t n_walks, uint32_t length, uint32_t length_kind,
+                  const uint32_t *start_nodes, uint64_t n_start_nodes, uint64_t seed, uint8_t *out_bases, uint32_t *out_len,
+                  uint32_t *out_flags, uint32_t *out_history, uint32_t history_cap, uint32_t *out_history_len,
+                  uint32_t *out_node_usage);
 struct MappingSink;
 // by_ratio: use_max_ratio of forward_sparse (forward.rs:93-154); false = fixed warm-up + top n_active_nodes
 void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_logp, double *out_total,

@@ -367,6 +367,78 @@ class PHMMModel:
             _ptr(usage) if want_usage and usage.size else None))
         return lp, plp, path, counts, usage
 
+    _GEN_KINDS = {"state_count": 0, "endable": 1, "emit_count": 2}
+
+    def sample_reads_raw(self, first_index: int, n_walks: int, length: int, kind: str = "state_count", start_nodes=None,
+                         seed: int = 0, want_history: bool = False, want_usage: bool = False):
+        """phmm_sample_reads (include/phmm_amd_generate.h) for the walks first_index .. first_index + n_walks - 1
+        -> (bases[n_walks, length + 1] uint8 padded with 0, len[n_walks], flags[n_walks], history[n_walks, cap] | None,
+        history_len[n_walks] | None, usage[n_nodes] | None); cap = length + 1, or 8 * length + 65 under emit_count, so
+        no history is truncated."""
+        n, length = int(n_walks), int(length)
+        sn = None if start_nodes is None else np.ascontiguousarray(start_nodes, dtype=np.uint32).reshape(-1)
+        bases = np.empty((n, length + 1), dtype=np.uint8)
+        ln, fl = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        cap = (8 * length + 65 if kind == "emit_count" else length + 1) if want_history else 0
+        hist = np.empty((n, cap), dtype=np.uint32) if want_history else None
+        hl = np.empty(n, dtype=np.uint32) if want_history else None
+        usage = np.empty(self.n_nodes, dtype=np.uint32) if want_usage else None
+        _ffi.check(_ffi.lib().phmm_sample_reads(
+            self._h, int(first_index), n, length, self._GEN_KINDS[kind], _ptr(sn), 0 if sn is None else sn.size,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(bases) if n else None, _ptr(ln) if n else None, _ptr(fl) if n else None,
+            _ptr(hist) if want_history and n else None, cap, _ptr(hl) if want_history and n else None, _ptr(usage)))
+        return bases, ln, fl, hist, hl, usage
+
+    def sample_reads(self, length: int, kind: str = "state_count", n_reads: Optional[int] = None,
+                     total_bases: Optional[int] = None, start_nodes=None, seed: int = 0, want_history: bool = False,
+                     batch: int = 4096):
+        """Reads drawn from the model on the device: sample_by_profile (sample.rs:198-235) over phmm_sample_reads
+        (include/phmm_amd_generate.h, which writes out the walk, the random stream and the draw rule)
+        -> (ReadCollection, info).
+        kind: 'state_count', 'endable' or 'emit_count' (ReadLength::StateCount / Endable / EmitCount of `length`);
+        start_nodes: StartPoints::Custom (None: the walks start in MatchBegin).  The walks 0, 1, 2, .. of `seed` are
+        taken in index order, `batch` per call; a walk without bases is dropped, and under 'emit_count' a walk whose
+        length is not `length` (the reference's retry loop).  Exactly one of n_reads (ReadAmount::Count) and total_bases
+        (ReadAmount::TotalBases: walks are accepted until their bases reach the total, the read that crosses it kept)
+        ends the loop.  info = dict(walk_index[R], flags[R] (PHMM_GEN_* bits), n_walks = the walks consumed, the last
+        accepted one included, and with want_history history = [uint32 words per read]: (node << 2) | 0 Match / 1 Ins /
+        2 Del, PATH_INS_BEGIN, or 0xfffffffc for End).  The result does not depend on batch."""
+        if (n_reads is None) == (total_bases is None):
+            raise ValueError("give exactly one of n_reads and total_bases")
+        if kind not in self._GEN_KINDS:
+            raise ValueError("kind is 'state_count', 'endable' or 'emit_count'")
+        batch = max(1, int(batch))
+        reads: List[bytes] = []
+        index: List[int] = []
+        flags: List[int] = []
+        history: List[np.ndarray] = []
+        got, first, consumed = 0, 0, 0
+
+        def more():
+            return len(reads) < n_reads if n_reads is not None else got < total_bases
+        while more():
+            if first - consumed > (1 << 20):
+                raise RuntimeError("sample_reads: no walk accepted among the last 2^20")
+            bases, ln, fl, hist, hl, _ = self.sample_reads_raw(first, batch, length, kind, start_nodes, seed, want_history)
+            for w in range(batch):
+                n = int(ln[w])
+                if n == 0 or (kind == "emit_count" and n != length):
+                    continue
+                reads.append(bases[w, :n].tobytes())
+                index.append(first + w)
+                flags.append(int(fl[w]))
+                if want_history:
+                    history.append(hist[w, :int(hl[w])].copy())
+                got += n
+                consumed = first + w + 1
+                if not more():
+                    break
+            first += batch
+        info = dict(walk_index=np.array(index, dtype=np.uint64), flags=np.array(flags, dtype=np.uint32), n_walks=consumed)
+        if want_history:
+            info["history"] = history
+        return ReadCollection(reads), info
+
     def q_score_exact(self, edge_freqs: np.ndarray, init_freqs: np.ndarray):
         """q_score_exact (src/hmmv2/q.rs:66-96) -> (init, trans, prior); QScore::total() is their sum."""
         ef = np.ascontiguousarray(edge_freqs, dtype=np.float64)

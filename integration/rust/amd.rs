@@ -430,6 +430,76 @@ impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
         out
     }
 
+    /// sample_by_profile (sample.rs:198-235) on the device (phmm_sample_reads, include/phmm_amd_generate.h): the walks
+    /// 0, 1, 2, .. of profile.seed in index order, `batch` per call; a walk without bases is dropped, and under
+    /// ReadLength::EmitCount a walk whose length differs (the reference's retry loop).  The random stream is the
+    /// header's, not Xoshiro256PlusPlus: the reads follow the same law as the reference's, not the same bits.
+    /// Unverified, like the rest of this shim: it has not been compiled here.
+    pub fn sample_reads_amd(&self, profile: &SampleProfile, batch: usize) -> Historys {
+        let m = AmdModel::new(self);
+        let (length, kind) = match profile.length {
+            ReadLength::StateCount(c) => (c, PHMM_GEN_STATE_COUNT),
+            ReadLength::Endable(c) => (c, PHMM_GEN_ENDABLE),
+            ReadLength::EmitCount(c) => (c, PHMM_GEN_EMIT_COUNT),
+        };
+        let starts: Vec<u32> = match &profile.start_points {
+            StartPoints::Custom(nodes) => nodes.iter().map(|v| v.index() as u32).collect(),
+            StartPoints::Random => Vec::new(),
+            StartPoints::AllStartPoints => panic!("StartPoints::AllStartPoints is not resolved until sample_by_profile"),
+        };
+        let cap = if kind == PHMM_GEN_EMIT_COUNT { 8 * length + 65 } else { length + 1 };
+        let (mut bases, mut len) = (vec![0u8; batch * (length + 1)], vec![0u32; batch]);
+        let (mut hist, mut hist_len) = (vec![PHMM_PATH_NONE; batch * cap], vec![0u32; batch]);
+        let mut historys = Vec::new();
+        let (mut first, mut total_bases) = (0u64, 0usize);
+        let more = |n: usize, b: usize| match profile.read_amount {
+            ReadAmount::Count(n_reads) => n < n_reads,
+            ReadAmount::TotalBases(required) => b < required,
+        };
+        while more(historys.len(), total_bases) {
+            check(unsafe {
+                phmm_sample_reads(m.0, first, batch as u64, length as u32, kind,
+                                  if starts.is_empty() { ptr::null() } else { starts.as_ptr() }, starts.len() as u64,
+                                  profile.seed, bases.as_mut_ptr(), len.as_mut_ptr(), ptr::null_mut(), hist.as_mut_ptr(),
+                                  cap as u32, hist_len.as_mut_ptr(), ptr::null_mut())
+            });
+            for w in 0..batch {
+                let n = len[w] as usize;
+                if n == 0 || (kind == PHMM_GEN_EMIT_COUNT && n != length) {
+                    continue;
+                }
+                let mut history = History::new();
+                let mut emitted = bases[w * (length + 1)..w * (length + 1) + n].iter();
+                for &code in &hist[w * cap..w * cap + hist_len[w] as usize] {
+                    let state = match code {
+                        PHMM_GEN_END => State::End,
+                        PHMM_PATH_INS_BEGIN => State::InsBegin,
+                        _ => {
+                            let v = NodeIndex::new((code >> 2) as usize);
+                            match code & 3 {
+                                0 => State::Match(v),
+                                1 => State::Ins(v),
+                                _ => State::Del(v),
+                            }
+                        }
+                    };
+                    let emission = match state {
+                        State::Match(_) | State::Ins(_) | State::InsBegin => Emission::Base(*emitted.next().unwrap()),
+                        _ => Emission::Empty,
+                    };
+                    history.push(state, emission);
+                }
+                total_bases += n;
+                historys.push(history);
+                if !more(historys.len(), total_bases) {
+                    break;
+                }
+            }
+            first += batch as u64;
+        }
+        Historys(historys)
+    }
+
     /// q_score_exact (q.rs:66-96) from the transition posteriors over the lists -> (init, trans, prior)
     pub fn q_score_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings) -> (f64, f64, f64) {
         let (ef, nf) = self.to_edge_and_init_freqs_with_mapping_amd(reads, mappings);

@@ -175,6 +175,12 @@ extern "C" {
                                               n_samples: u32, seed: u64, out_logp: *mut f64, out_path_logp: *mut f64,
                                               out_path: *mut u32, out_counts: *mut u32, out_node_usage: *mut u32) -> c_int;
 
+    // (include/phmm_amd_generate.h, the fifth companion header)
+    pub fn phmm_sample_reads(m: *mut phmm_model, first_index: u64, n_walks: u64, length: u32, length_kind: u32,
+                             start_nodes: *const u32, n_start_nodes: u64, seed: u64, out_bases: *mut u8, out_len: *mut u32,
+                             out_flags: *mut u32, out_history: *mut u32, history_cap: u32, out_history_len: *mut u32,
+                             out_node_usage: *mut u32) -> c_int;
+
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
     // (include/phmm_amd_share.h, the third companion header)
@@ -183,3 +189,7 @@ extern "C" {
 
 pub const PHMM_PATH_NONE: u32 = 0xffff_ffff;
 pub const PHMM_PATH_INS_BEGIN: u32 = 0xffff_fffd;
+pub const PHMM_GEN_END: u32 = 0xffff_fffc;
+pub const PHMM_GEN_STATE_COUNT: u32 = 0;
+pub const PHMM_GEN_ENDABLE: u32 = 1;
+pub const PHMM_GEN_EMIT_COUNT: u32 = 2;
