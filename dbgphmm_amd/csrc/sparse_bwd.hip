@@ -693,17 +693,6 @@ void backward_sparse_impl(phmm_model *m, const uint8_t *bases, const uint64_t *o
     if (out_logp) std::memcpy(out_logp, res.data(), sizeof(double) * R);
 }
 
-void put_any(double *dst, const double *src, size_t n) {
-    if (!dst) return;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, dst) == hipSuccess && at.type == hipMemoryTypeDevice) {
-        HIP_CHECK(hipMemcpy(dst, src, n * sizeof(double), hipMemcpyHostToDevice));
-    } else {
-        (void)hipGetLastError();
-        std::memcpy(dst, src, n * sizeof(double));
-    }
-}
-
 }  // namespace
 
 // to_full_prob_sparse_backward (freq.rs:153-163): per-read ln P from backward_sparse, and their sum
@@ -712,8 +701,8 @@ void full_prob_sparse_backward(phmm_model *m, const phmm_reads *reads, double *o
     backward_sparse_impl(m, reads->bases.data(), reads->off.data(), reads->R, lp.data(), nullptr);
     double tot = 0.0;
     for (double v : lp) tot += v;
-    put_any(out_logp, lp.data(), lp.size());
-    put_any(out_total, &tot, 1);
+    put_doubles(out_logp, lp.data(), lp.size());
+    put_doubles(out_total, &tot, 1);
 }
 
 // backward_sparse tables of ONE read (parity tests / `inspect`-style tools): [L][N] natural-log arrays
@@ -1002,8 +991,8 @@ void run_sparse(phmm_model *m, const phmm_reads *reads, double *out_lf, double *
         }
         g0 += ngc;
     }
-    put_any(out_lf, lf.data(), lf.size());
-    put_any(out_lb, lb.data(), lb.size());
+    put_doubles(out_lf, lf.data(), lf.size());
+    put_doubles(out_lb, lb.data(), lb.size());
     if (out_nf) copy_out(out_nf, freq.p, sizeof(double) * m->N);
 }
 

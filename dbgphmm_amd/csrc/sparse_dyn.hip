@@ -968,11 +968,17 @@ void full_prob_reads_sparse(phmm_model *m, const phmm_reads *reads, double *out_
             const uint64_t n_pos = lane_pos0[lanes];
             uint64_t sparse_pos = 0;
             for (uint32_t gi : sparse_lanes) sparse_pos += (uint64_t)(hl[gi] - hsw[gi]);
-            uint64_t pool_cap = std::max<uint64_t>(fpool.bytes, sparse_pos * 1024 + (uint64_t)sparse_lanes.size() * 65536 + (1u << 20));
+            // The buffer holds the pool plus POOL_PAD bytes (the backward kernel fetches 1 KB from a record's start
+            // whatever its size).  The capacity taken back from a buffer of an earlier call leaves the pad out: fed
+            // back, it asked for 4 KB more than the buffer held on every chunk of every call, and the grow-only
+            // reserve freed and reallocated the whole pool each time.
+            constexpr uint64_t POOL_PAD = 4096;
+            const uint64_t pool_held = fpool.bytes > POOL_PAD ? (uint64_t)fpool.bytes - POOL_PAD : 0;
+            uint64_t pool_cap = std::max<uint64_t>(pool_held, sparse_pos * 1024 + (uint64_t)sparse_lanes.size() * 65536 + (1u << 20));
             const size_t o_stop = o_cnt;  // the per-lane count array of the warm-up is free again
             fa.stop = (int *)(wp + o_stop);
             for (int attempt = 0;; attempt++) {
-                fpool.reserve(pool_cap + 4096);  // (the backward kernel fetches 1 KB from a record's start whatever its size)
+                fpool.reserve(pool_cap + POOL_PAD);
                 fpool_meta.reserve(sizeof(unsigned long long) + sizeof(uint64_t) * (n_pos + 1) * 2);
                 HIP_CHECK(hipMemsetAsync(fpool_meta.p, 0, sizeof(unsigned long long) + sizeof(uint64_t) * (n_pos + 1) * 2, s));
                 fa.pool.base = fpool.as<uint8_t>();

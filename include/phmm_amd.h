@@ -14,6 +14,15 @@
  *  - input pointers are HOST pointers.  Output pointers may be host OR device
  *    pointers (detected with hipPointerGetAttributes): device outputs let the caller
  *    all-reduce `node_freq` / totals over RCCL without a host round trip.
+ *    Where the text of an entry point says "host pointer" for an output (phmm_likelihood_current's copy_nums,
+ *    phmm_mappings_export, the single-read table dumps, phmm_q_score_exact) it is written with a plain host copy.
+ *  - streams: phmm_set_stream() is a per-thread setting.  All device work of a call -- its kernels, the worker
+ *    and side streams it uses inside, the copies into device outputs -- is ordered after everything the thread's
+ *    stream held when the call was made, and when the call returns every output is complete ON THAT STREAM:
+ *    work queued on it afterwards, or anything behind a hipStreamSynchronize of it, sees the results.  (As built
+ *    today every compute entry point also synchronises the stream before it returns, because it reads error
+ *    words and totals back; a caller should rely on the stream order only.)  Nothing is ordered against other
+ *    streams, the NULL stream included, when the caller's stream is hipStreamNonBlocking.
  *  - every function returns 0 on success or a negative PHMM_E* code;
  *    phmm_last_error() returns the message (thread-local).  Nothing unwinds across
  *    the ABI.  Where the reference panics (empty read, capacity overflow) the call
@@ -66,7 +75,11 @@ const char *phmm_version(void);
 int phmm_device_count(void);
 /* select the device for this thread's subsequent calls (one process per GPU: LOCAL_RANK) */
 int phmm_set_device(int device);
-/* run subsequent work of this thread on the given hipStream_t (NULL = default stream) */
+/* run subsequent work of this thread on the given hipStream_t (NULL = default stream).  Per thread: a thread that
+ * never called it is on the NULL stream whatever other threads hold, and the setting stays until the thread sets
+ * another.  The stream must outlive the calls made on it; see "streams" in the conventions above for the ordering a
+ * call keeps.  The workspaces belong to the device, not to the stream: calls on different streams are serialised and
+ * each leaves nothing running on the workspaces when it returns. */
 int phmm_set_stream(void *hip_stream);
 /* upper bound (bytes) for the workspace of one call; 0 = automatic: the adaptive flow plans 95 % of (free + already
  * held) HBM for ALL its buffers, the dense drivers take 90 % for their tables */

@@ -838,10 +838,12 @@ def test_destroyed_mappings_leave_their_device_buffers_for_the_next_call(gpu_lib
     spare = L.phmm_workspace_bytes() - held
     assert spare >= a1[2].nbytes
     mp2, nf2 = gm.generate_mappings(rc, None, True)
-    assert L.phmm_workspace_bytes() - held < 1 << 16  # the spares went into mp2 (a hinted call may grow a control array)
+    print("workspace growth of the second call:", L.phmm_workspace_bytes() - held, "spare bytes:", spare)
+    assert L.phmm_workspace_bytes() == held  # the spares went into mp2, and no workspace buffer grew on a second call
     assert same_mappings(a1, mp2.arrays()) and np.array_equal(nf1, nf2)
     del mp2
-    assert spare <= L.phmm_workspace_bytes() - held < spare + (1 << 16)
+    print("spare bytes after the second destroy:", L.phmm_workspace_bytes() - held)
+    assert L.phmm_workspace_bytes() - held == spare  # the same three buffers wait again
     _ffi.check(L.phmm_release_workspace())
     assert L.phmm_workspace_bytes() == 0
     mp3, _ = gm.generate_mappings(rc, None, True)
