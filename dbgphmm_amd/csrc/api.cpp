@@ -1056,6 +1056,37 @@ int phmm_run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, c
     });
 }
 
+int phmm_run_with_mapping_alignments(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
+                                     uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_counts,
+                                     phmm_alignments **out) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        if (n_samples > (uint32_t)PHMM_SAMPLE_MAX) PHMM_THROW(PHMM_EINVAL, "n_samples must be 0..64");
+        check_mapping_nodes(m, mp, reads);
+        std::unique_ptr<phmm_alignments> h(out ? new phmm_alignments() : nullptr);
+        if (h) h->device = m->pool->device;
+        if (reads->R) run_with_mapping_alignments(m, reads, mp, n_samples, seed, out_logp, out_path_logp, out_counts, h.get());
+        if (out) *out = h.release();  // (a refusal has thrown: *out stays as it was)
+    });
+}
+
+uint64_t phmm_alignments_count(const phmm_alignments *a) { return a ? a->A : 0; }
+uint64_t phmm_alignments_total_ops(const phmm_alignments *a) { return a ? a->total_ops : 0; }
+uint64_t phmm_alignments_total_runs(const phmm_alignments *a) { return a ? a->total_runs : 0; }
+
+int phmm_alignments_export(const phmm_alignments *a, uint64_t *op_off, uint32_t *ops, uint64_t *run_off, uint32_t *run_node,
+                           uint32_t *run_len) {
+    return guarded([&] {
+        if (!a) PHMM_THROW(PHMM_EINVAL, "NULL alignments");
+        int dev = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        if (dev != a->device) PHMM_THROW(PHMM_EINVAL, "the alignments live on another device (phmm_set_device)");
+        alignments_export(a, op_off, ops, run_off, run_node, run_len);
+    });
+}
+
+void phmm_alignments_destroy(phmm_alignments *a) { delete a; }
+
 int phmm_sample_reads(phmm_model *m, uint64_t first_index, uint64_t n_walks, uint32_t length, uint32_t length_kind,
                       const uint32_t *start_nodes, uint64_t n_start_nodes, uint64_t seed, uint8_t *out_bases,
                       uint32_t *out_len, uint32_t *out_flags, uint32_t *out_history, uint32_t history_cap,

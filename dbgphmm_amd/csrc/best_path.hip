@@ -3,8 +3,9 @@
 // Host flow.  The reads are cut into chunks of consecutive reads whose back-pointer records (16 bytes per list entry)
 // and, for a host out_path, staged rows fit the workspace budget (phmm_set_workspace_limit; table_budget otherwise).
 // Per chunk: the forward kernel of the <= 64 class and of the 400 class over the chunk's reads, then the traceback
-// over all of them, then the rows of a host out_path go out.  ln P and the counts of all reads stay in the workspace
-// until the last chunk is done.  A read's results depend on the read and its lists alone, so the chunking shows nowhere.
+// over all of them, then the rows of a host out_path go out -- or, with a RowSink (alignments.hip), the staged rows are
+// handed to it on the device.  ln P and the counts of all reads stay in the workspace until the last chunk is done.
+// A read's results depend on the read and its lists alone, so the chunking shows nowhere.
 #include <algorithm>
 #include <cstring>
 
@@ -46,7 +47,7 @@ struct CallTimer {  // device time of the whole call on its stream (index 2 of p
 }  // namespace
 
 void run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_logp,
-                                uint32_t *out_path, uint32_t *out_counts) {
+                                uint32_t *out_path, uint32_t *out_counts, RowSink *sink) {
     hipStream_t s = current_stream();
     CallStats &st = stats();
     st = CallStats();
@@ -109,7 +110,7 @@ void run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, const ph
     HIP_CHECK(hipMemcpyAsync(ent.data(), cp + o_ent, sizeof(uint64_t) * (R + 1), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
 
-    const bool stage_rows = out_path && n_pos && !is_device_pointer(out_path);
+    const bool stage_rows = sink ? n_pos != 0 : out_path && n_pos && !is_device_pointer(out_path);
     const uint64_t fixed = cb + sizeof(double) * ((uint64_t)N + E), limit = table_budget(*m->pool);
     const uint64_t budget = limit > fixed ? limit - fixed : 0;
     auto read_bytes = [&](uint64_t r) {
@@ -146,7 +147,8 @@ void run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, const ph
         hipLaunchKernelGGL(best_path_traceback_kernel, dim3((unsigned)((r1 - r0 + 63) / 64)), dim3(64), 0, s, a);
         HIP_CHECK(hipGetLastError());
         st.launches[2]++;
-        if (stage_rows && n_rows)
+        if (sink) sink->chunk(r0, r1, stage_rows ? rows.as<uint32_t>() : nullptr, n_rows, stride);
+        else if (stage_rows && n_rows)
             HIP_CHECK(hipMemcpyAsync(out_path + reads->off[r0] * stride, rows.p, sizeof(uint32_t) * stride * n_rows,
                                      hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));

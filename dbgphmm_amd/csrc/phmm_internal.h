@@ -16,6 +16,7 @@
 #include "../../include/phmm_amd_share.h"
 #include "../../include/phmm_amd_sample.h"
 #include "../../include/phmm_amd_generate.h"
+#include "../../include/phmm_amd_align.h"
 
 namespace phmm {
 
@@ -342,6 +343,15 @@ namespace phmm {
 void mappings_materialize_host(const phmm_mappings *mp);
 }
 
+// The alignment records of one phmm_run_with_mapping_alignments call (include/phmm_amd_align.h).  The arrays belong to
+// the handle, not to the device workspace, and the handle borrows nothing.
+struct phmm_alignments {
+    uint64_t A = 0, total_ops = 0, total_runs = 0;
+    int device = -1;
+    phmm::DevBuf d_op_off, d_run_off;           // u64[A+1]
+    phmm::DevBuf d_ops, d_run_node, d_run_len;  // u32[total_ops], u32[total_runs] twice (grown chunk by chunk)
+};
+
 // The sampler's state at one k (MultiDbg::to_likelihood, posterior.rs:247-255, through the greedy search of
 // sample_posterior, posterior.rs:314-417): the current copy-number vector and every read's ln P under it, on the device.
 // The value of read r under the current vector is val[r] + ln(T_at[r] / T): val[r] is what the kernels gave when r was
@@ -515,13 +525,26 @@ void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_m
                             double *out_ef, double *out_if);
 void run_with_mapping_states(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
                              double *out_state_logp, uint32_t *out_best);
+// A device consumer of the rows of the two calls below (alignments.hip).  With a sink every chunk's rows are staged in
+// the workspace, as for a host out_path, and handed over on the call's stream behind the walk in place of the copy out.
+struct RowSink {
+    virtual ~RowSink() = default;
+    // the reads r0 .. r1-1; row of base g in plane s: rows[(s * plane_rows + g - reads->off[r0]) * stride]
+    virtual void chunk(uint64_t r0, uint64_t r1, const uint32_t *rows, uint64_t plane_rows, uint32_t stride) = 0;
+};
 // the best path of every read over its lists and its ln P (best_path.hip)
 void run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_logp,
-                                uint32_t *out_path, uint32_t *out_counts);
+                                uint32_t *out_path, uint32_t *out_counts, RowSink *sink = nullptr);
 // n_samples draws from the posterior over paths of every read over its lists (sample_paths.hip)
 void run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
                                    uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_path,
-                                   uint32_t *out_counts, uint32_t *out_node_usage);
+                                   uint32_t *out_counts, uint32_t *out_node_usage, RowSink *sink = nullptr);
+// the same paths as alignment records (alignments.hip); h == nullptr: scores and counts only
+void run_with_mapping_alignments(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
+                                 uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_counts,
+                                 phmm_alignments *h);
+void alignments_export(const phmm_alignments *h, uint64_t *op_off, uint32_t *ops, uint64_t *run_off, uint32_t *run_node,
+                       uint32_t *run_len);
 // reads drawn from the model, one walk per lane (sample_reads.hip)
 void sample_reads(phmm_model *m, uint64_t first_index, uint64_t n_walks, uint32_t length, uint32_t length_kind,
                   const uint32_t *start_nodes, uint64_t n_start_nodes, uint64_t seed, uint8_t *out_bases, uint32_t *out_len,

@@ -5,8 +5,9 @@
 // list entry), InsBegin values (8 bytes per base) and, for a host out_path, staged rows (n_samples planes) fit the
 // workspace budget (phmm_set_workspace_limit; table_budget otherwise).  Per chunk: the forward kernel of the <= 64
 // class and of the 400 class over the chunk's reads, then the walk over all of them, then the rows of a host out_path
-// go out plane by plane.  ln Z, the path values and the counts of all reads stay in the workspace until the last chunk
-// is done.  A read's results depend on the read, its lists, its index and the seed alone, so the chunking shows nowhere.
+// go out plane by plane -- or, with a RowSink (alignments.hip), the staged planes are handed to it on the device.
+// ln Z, the path values and the counts of all reads stay in the workspace until the last chunk is done.  A read's
+// results depend on the read, its lists, its index and the seed alone, so the chunking shows nowhere.
 // (The column type, the pointer test and the call timer repeat best_path's: best_path_kernel.h defines kernels that are
 // no templates, so it can be part of one translation unit only, and the best-path call stays as it is.)
 #include <algorithm>
@@ -51,7 +52,7 @@ struct SampleTimer {  // device time of the whole call on its stream (index 2 of
 
 void run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
                                    uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_path,
-                                   uint32_t *out_counts, uint32_t *out_node_usage) {
+                                   uint32_t *out_counts, uint32_t *out_node_usage, RowSink *sink) {
     hipStream_t s = current_stream();
     CallStats &st = stats();
     st = CallStats();
@@ -130,7 +131,7 @@ void run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const
     HIP_CHECK(hipMemcpyAsync(ent.data(), cp + o_ent, sizeof(uint64_t) * (R + 1), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
 
-    const bool stage_rows = out_path && n_pos && !sample_is_device_pointer(out_path);
+    const bool stage_rows = sink ? n_pos != 0 : out_path && n_pos && !sample_is_device_pointer(out_path);
     const uint64_t fixed = cb + sizeof(double) * ((uint64_t)N + E) + (out_node_usage && !usage_in_place ? sizeof(uint32_t) * S * N : 0),
                    limit = table_budget(*m->pool);
     const uint64_t budget = limit > fixed ? limit - fixed : 0;
@@ -173,7 +174,8 @@ void run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const
         hipLaunchKernelGGL(sample_walk_kernel, dim3((unsigned)(r1 - r0)), dim3(64), 0, s, a);
         HIP_CHECK(hipGetLastError());
         st.launches[2]++;
-        if (stage_rows && n_rows)
+        if (sink) sink->chunk(r0, r1, stage_rows ? rows.as<uint32_t>() : nullptr, n_rows, stride);
+        else if (stage_rows && n_rows)
             HIP_CHECK(hipMemcpy2DAsync(out_path + reads->off[r0] * stride, sizeof(uint32_t) * stride * n_pos, rows.p,
                                        sizeof(uint32_t) * stride * n_rows, sizeof(uint32_t) * stride * n_rows, S,
                                        hipMemcpyDeviceToHost, s));

@@ -119,6 +119,77 @@ def read_map(path_or_file) -> Tuple[List[bytes], Tuple[np.ndarray, np.ndarray, n
                                         np.array(logp, dtype=np.float64))
 
 
+# ------------------------------------------------------------------------------------------------ alignment records
+_OPS = {"I": 1, "D": 2, "=": 7, "X": 8}
+
+
+def write_alignments(path_or_file, alignments, logp, names: Optional[Sequence[str]] = None) -> None:
+    """One tab-separated line per alignment of PHMMModel.run_with_mapping_alignments: read name (or index), sample,
+    ln P, CIGAR string, walk as ``node+len,...``; ``*`` for an empty CIGAR or walk (a read without a path).  logp holds
+    one value per read (the best ln P, or ln Z: written on each of the read's samples) or one per alignment
+    (path_logp[R, S]).  The nodes of a walk are k-mers that overlap by k-1: this is a format of its own."""
+    A, planes = len(alignments), max(alignments.n_samples, 1)
+    lp = np.asarray(logp, dtype=np.float64).reshape(-1)
+    if lp.shape[0] not in (A, alignments.n_reads):
+        raise ValueError("logp holds neither one value per read nor one per alignment")
+    per_read = lp.shape[0] != A
+    fh = _open(path_or_file, "w") if isinstance(path_or_file, str) else path_or_file
+    try:
+        fh.write("# dbgphmm_amd alignments\n")
+        fh.write(f"# n_reads={alignments.n_reads} n_samples={alignments.n_samples}\n")
+        fh.write("# read\tsample\tlogp\tcigar\twalk\n")
+        for a in range(A):
+            r, s = divmod(a, planes)
+            name = str(r) if names is None else names[r]
+            walk = ",".join(f"{v}+{n}" for v, n in alignments.walk(a))
+            fh.write(f"{name}\t{s}\t{float(lp[r if per_read else a])!r}\t{alignments.cigar_string(a) or '*'}\t{walk or '*'}\n")
+    finally:
+        if isinstance(path_or_file, str):
+            fh.close()
+
+
+def read_alignments(path_or_file):
+    """-> (names[R], logp[A], Alignments) of a file write_alignments wrote; lines come in (read, sample) order"""
+    from .model import Alignments
+    fh = _open(path_or_file, "r") if isinstance(path_or_file, str) else path_or_file
+    names: List[str] = []
+    n_samples = None
+    logp, op_off, ops, run_off, run_node, run_len = [], [0], [], [0], [], []
+    try:
+        for line in fh:
+            if line.startswith("# n_reads="):
+                n_samples = int(line.split("n_samples=")[1])
+            if not line.strip() or line.startswith("#"):
+                continue
+            name, s, lp, cigar, walk = line.rstrip("\n").split("\t")
+            if int(s) != len(logp) % max(n_samples or 0, 1) or (int(s) and name != names[-1]):
+                raise ValueError("alignment lines out of order")
+            if int(s) == 0:
+                names.append(name)
+            logp.append(float(lp))
+            if cigar != "*":
+                num = ""
+                for ch in cigar:
+                    if ch.isdigit():
+                        num += ch
+                    else:
+                        ops.append((int(num) << 4) | _OPS[ch])
+                        num = ""
+            if walk != "*":
+                for item in walk.split(","):
+                    v, n = item.split("+")
+                    run_node.append(int(v))
+                    run_len.append(int(n))
+            op_off.append(len(ops))
+            run_off.append(len(run_node))
+    finally:
+        if isinstance(path_or_file, str):
+            fh.close()
+    if n_samples is None:
+        raise ValueError("no '# n_reads= n_samples=' line")
+    return names, np.array(logp), Alignments.from_arrays(len(names), n_samples, op_off, ops, run_off, run_node, run_len)
+
+
 # ------------------------------------------------------------------------------------------------ DBG
 @dataclass
 class DbgFile:

@@ -180,6 +180,85 @@ def path_states(mappings: "Mappings", read: int, path: np.ndarray) -> List[Tuple
     return out
 
 
+class Alignments:
+    """The alignment records of PHMMModel.run_with_mapping_alignments (include/phmm_amd_align.h): per alignment
+    a = read * max(n_samples, 1) + sample a CIGAR -- runs (len, op) over the path's events, op 7 '=', 8 'X', 1 'I',
+    2 'D' -- and a node walk -- runs (first node, len) of consecutive node ids over its Match and Del states.  The
+    records stay on the device until arrays() is first called."""
+
+    def __init__(self, handle, n_reads: int, n_samples: int):
+        self._h = handle
+        self.n_reads, self.n_samples = int(n_reads), int(n_samples)
+        self._cache = None
+
+    @staticmethod
+    def from_arrays(n_reads: int, n_samples: int, op_off, ops, run_off, run_node, run_len) -> "Alignments":
+        """records that are on the host already (a file read back, a test)"""
+        a = Alignments(None, n_reads, n_samples)
+        a._cache = (np.asarray(op_off, dtype=np.uint64), np.asarray(ops, dtype=np.uint32),
+                    np.asarray(run_off, dtype=np.uint64), np.asarray(run_node, dtype=np.uint32),
+                    np.asarray(run_len, dtype=np.uint32))
+        assert a._cache[0].shape[0] == len(a) + 1 == a._cache[2].shape[0]
+        return a
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            from . import _ffi_align
+            _ffi_align.lib().phmm_alignments_destroy(self._h)
+            self._h = None
+
+    def __len__(self) -> int:
+        return self.n_reads * max(self.n_samples, 1)
+
+    def index(self, read: int, sample: int = 0) -> int:
+        return read * max(self.n_samples, 1) + sample
+
+    def arrays(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(op_off[A + 1], ops, run_off[A + 1], run_node, run_len), copied from the device on the first call"""
+        if self._cache is None:
+            from . import _ffi_align
+            L = _ffi_align.lib()
+            A, n_ops, n_runs = (int(L.phmm_alignments_count(self._h)), int(L.phmm_alignments_total_ops(self._h)),
+                                int(L.phmm_alignments_total_runs(self._h)))
+            op_off, run_off = np.empty(A + 1, dtype=np.uint64), np.empty(A + 1, dtype=np.uint64)
+            ops, rn, rl = (np.empty(max(n_ops, 1), dtype=np.uint32), np.empty(max(n_runs, 1), dtype=np.uint32),
+                           np.empty(max(n_runs, 1), dtype=np.uint32))
+            _ffi.check(L.phmm_alignments_export(self._h, _ptr(op_off), _ptr(ops), _ptr(run_off), _ptr(rn), _ptr(rl)))
+            self._cache = (op_off, ops[:n_ops], run_off, rn[:n_runs], rl[:n_runs])
+        return self._cache
+
+    def cigar(self, a: int) -> List[Tuple[int, int]]:
+        op_off, ops = self.arrays()[:2]
+        return [(w >> 4, w & 15) for w in ops[int(op_off[a]):int(op_off[a + 1])].tolist()]
+
+    def cigar_string(self, a: int) -> str:
+        from ._ffi_align import OP_CHARS
+        return "".join(f"{n}{OP_CHARS[op]}" for n, op in self.cigar(a))
+
+    def walk(self, a: int) -> List[Tuple[int, int]]:
+        _, _, run_off, rn, rl = self.arrays()
+        e0, e1 = int(run_off[a]), int(run_off[a + 1])
+        return list(zip(rn[e0:e1].tolist(), rl[e0:e1].tolist()))
+
+    def nodes(self, a: int) -> List[int]:
+        return [v for first, n in self.walk(a) for v in range(first, first + n)]
+
+    def states(self, a: int) -> List[Tuple[Optional[int], str]]:
+        """the (node, kind) sequence path_states gives for the alignment's read and plane: =, X and D take one step of
+        the walk each; an I sits on the last step's node, or is InsBegin before the first step"""
+        steps = iter(self.nodes(a))
+        out: List[Tuple[Optional[int], str]] = []
+        last = None
+        for n, op in self.cigar(a):
+            for _ in range(n):
+                if op == 1:
+                    out.append((None, "IB") if last is None else (last, "I"))
+                else:
+                    last = next(steps)
+                    out.append((last, "D" if op == 2 else "M"))
+        return out
+
+
 class PHMMModel:
     """PHMMModel<N, E> (src/hmmv2/common.rs:61-64) resident on one MI355X."""
 
@@ -366,6 +445,25 @@ class PHMMModel:
             _ptr(path) if want_path and path.size else None, _ptr(counts) if counts.size else None,
             _ptr(usage) if want_usage and usage.size else None))
         return lp, plp, path, counts, usage
+
+    def run_with_mapping_alignments(self, reads: ReadCollection, mappings: Mappings, n_samples: int = 0, seed: int = 0):
+        """The best path (n_samples = 0) or n_samples (1..64) sampled paths of every read over its lists as alignment
+        records, built on the device from rows that never leave it (include/phmm_amd_align.h)
+        -> (logp[R], path_logp[R, S] | None, counts[R, S', 4], Alignments), S' = max(n_samples, 1).
+        logp is the best ln P or ln Z; path_logp the ln P of each sample (None for the best path); counts the =, X, I, D
+        totals of each alignment; the walks are those run_with_mapping_best_path / run_with_mapping_sample_paths return
+        for the same arguments."""
+        from . import _ffi_align
+        R, S = len(reads), int(n_samples)
+        planes = max(S, 1)
+        lp = np.empty(R)
+        plp = np.empty((R, S)) if S else None
+        counts = np.empty((R, planes, 4), dtype=np.uint32)
+        h = C.c_void_p()
+        _ffi.check(_ffi_align.lib().phmm_run_with_mapping_alignments(
+            self._h, reads._h, mappings._h, S, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(lp),
+            _ptr(plp) if S and plp.size else None, _ptr(counts) if counts.size else None, C.byref(h)))
+        return lp, plp, counts, Alignments(h, R, S)
 
     _GEN_KINDS = {"state_count": 0, "endable": 1, "emit_count": 2}
 

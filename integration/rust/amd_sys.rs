@@ -60,6 +60,10 @@ pub struct phmm_mappings {
 pub struct phmm_likelihood {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct phmm_alignments {
+    _p: [u8; 0],
+}
 
 #[link(name = "phmm_amd")]
 /// phmm_likelihood_current_groups: a node-form move changed part of the group
@@ -180,6 +184,17 @@ extern "C" {
                              start_nodes: *const u32, n_start_nodes: u64, seed: u64, out_bases: *mut u8, out_len: *mut u32,
                              out_flags: *mut u32, out_history: *mut u32, history_cap: u32, out_history_len: *mut u32,
                              out_node_usage: *mut u32) -> c_int;
+
+    // (include/phmm_amd_align.h, the sixth companion header; phmm_alignments is an opaque handle like phmm_mappings)
+    pub fn phmm_run_with_mapping_alignments(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                            n_samples: u32, seed: u64, out_logp: *mut f64, out_path_logp: *mut f64,
+                                            out_counts: *mut u32, out: *mut *mut phmm_alignments) -> c_int;
+    pub fn phmm_alignments_count(a: *const phmm_alignments) -> u64;
+    pub fn phmm_alignments_total_ops(a: *const phmm_alignments) -> u64;
+    pub fn phmm_alignments_total_runs(a: *const phmm_alignments) -> u64;
+    pub fn phmm_alignments_export(a: *const phmm_alignments, op_off: *mut u64, ops: *mut u32, run_off: *mut u64,
+                                  run_node: *mut u32, run_len: *mut u32) -> c_int;
+    pub fn phmm_alignments_destroy(a: *mut phmm_alignments);
 
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
