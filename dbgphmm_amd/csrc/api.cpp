@@ -1043,6 +1043,30 @@ int phmm_run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, cons
     });
 }
 
+int phmm_run_with_mapping_weighted_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp,
+                                        const double *weights, const double *ib_weight, double *out_score,
+                                        uint32_t *out_path, uint32_t *out_counts) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        check_mapping_nodes(m, mp, reads);
+        if (!weights) PHMM_THROW(PHMM_EINVAL, "weights is NULL");
+        if (reads->R == 0) return;
+        run_with_mapping_weighted_path(m, reads, mp, weights, ib_weight, out_score, out_path, out_counts);
+    });
+}
+
+int phmm_run_with_mapping_mea_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double del_weight,
+                                   double *out_lf, double *out_score, uint32_t *out_path, uint32_t *out_counts,
+                                   double *out_weights) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        if (!(del_weight >= 0.0) || std::isinf(del_weight)) PHMM_THROW(PHMM_EINVAL, "del_weight must be finite and >= 0");
+        check_mapping_nodes(m, mp, reads);
+        if (reads->R == 0) return;
+        run_with_mapping_mea_path(m, reads, mp, del_weight, out_lf, out_score, out_path, out_counts, out_weights);
+    });
+}
+
 int phmm_run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
                                        uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_path,
                                        uint32_t *out_counts, uint32_t *out_node_usage) {

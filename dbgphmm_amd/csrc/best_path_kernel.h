@@ -243,8 +243,9 @@ __global__ void __launch_bounds__(64) best_path_forward_kernel(const BestPathArg
 }
 
 // One lane per read of the chunk.  A row is entry 0 = the emitting state, then the Del states behind it in the order
-// the path passes them, then PHMM_PATH_NONE; it is put together in registers and stored once.
-__global__ void __launch_bounds__(64) best_path_traceback_kernel(const BestPathArgs a) {
+// the path passes them, then PHMM_PATH_NONE; it is put together in registers and stored once.  (static, as the offsets
+// kernel below: mea_path.hip launches the two as well.)
+static __global__ void __launch_bounds__(64) best_path_traceback_kernel(const BestPathArgs a) {
     const uint32_t rd = a.r0 + blockIdx.x * 64 + threadIdx.x;
     if (rd >= a.r1) return;
     const uint64_t b0 = a.read_off[rd], len = a.read_off[rd + 1] - b0;
@@ -336,7 +337,7 @@ __global__ void __launch_bounds__(64) best_path_traceback_kernel(const BestPathA
 }
 
 // first list entry of every read (and the total behind the last)
-__global__ void __launch_bounds__(256) best_path_entry_offsets(const uint64_t *read_off, const uint64_t *map_pos_off,
+static __global__ void __launch_bounds__(256) best_path_entry_offsets(const uint64_t *read_off, const uint64_t *map_pos_off,
                                                                uint64_t R, uint64_t *out) {
     const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (r <= R) out[r] = map_pos_off[read_off[r]];

@@ -17,6 +17,7 @@
 #include "../../include/phmm_amd_sample.h"
 #include "../../include/phmm_amd_generate.h"
 #include "../../include/phmm_amd_align.h"
+#include "../../include/phmm_amd_mea.h"
 
 namespace phmm {
 
@@ -535,6 +536,14 @@ struct RowSink {
 // the best path of every read over its lists and its ln P (best_path.hip)
 void run_with_mapping_best_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_logp,
                                 uint32_t *out_path, uint32_t *out_counts, RowSink *sink = nullptr);
+// the legal walk of the largest summed weight, the caller's weights per entry and kind (mea_path.hip), and the same walk
+// on the posteriors of run_with_mapping_states, which stay on the device: the maximum-expected-accuracy path
+void run_with_mapping_weighted_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, const double *weights,
+                                    const double *ib_weight, double *out_score, uint32_t *out_path, uint32_t *out_counts,
+                                    RowSink *sink = nullptr);
+void run_with_mapping_mea_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double del_weight,
+                               double *out_lf, double *out_score, uint32_t *out_path, uint32_t *out_counts,
+                               double *out_weights, RowSink *sink = nullptr);
 // n_samples draws from the posterior over paths of every read over its lists (sample_paths.hip)
 void run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
                                    uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_path,

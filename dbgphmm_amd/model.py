@@ -422,6 +422,53 @@ class PHMMModel:
                                                                _ptr(counts)))
         return lp, path, counts
 
+    def run_with_mapping_weighted_path(self, reads: ReadCollection, mappings: Mappings, weights, ib_weight=None,
+                                       want_path: bool = True):
+        """The legal walk of the largest summed weight of every read over its lists (include/phmm_amd_mea.h): the path
+        family, the tie rule and the rows of run_with_mapping_best_path, with the model's logs deciding only which
+        transitions exist and the value of a path being the sum, left to right, of the caller's weights
+        -> (score[R], path[total_bases, stride] | None, counts[R, 4]).
+        weights[total_entries, 3]: one finite double per entry of the mappings' CSR and kind (Match, Ins, Del), the
+        layout of run_with_mapping_states' state_logp; ib_weight[total_bases]: the weight of InsBegin emitting each
+        base (None: 0).  Both may be numpy arrays or torch tensors, host or device.  score[r] = -inf: no legal path."""
+        from . import _ffi_mea
+        R = len(reads)
+        stride = int(self.param.n_max_gaps) + 2
+        if isinstance(weights, np.ndarray):
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if isinstance(ib_weight, np.ndarray):
+            ib_weight = np.ascontiguousarray(ib_weight, dtype=np.float64)
+        score = np.empty(R)
+        counts = np.empty((R, 4), dtype=np.uint32)
+        path = np.empty((reads.total_bases(), stride), dtype=np.uint32) if want_path else None
+        _ffi.check(_ffi_mea.lib().phmm_run_with_mapping_weighted_path(
+            self._h, reads._h, mappings._h, _ptr(weights), _ptr(ib_weight), _ptr(score),
+            _ptr(path) if want_path and path.size else None, _ptr(counts)))
+        return score, path, counts
+
+    def run_with_mapping_mea_path(self, reads: ReadCollection, mappings: Mappings, del_weight: float = 1.0,
+                                  want_path: bool = True, want_weights: bool = False):
+        """The maximum-expected-accuracy path of every read over its lists (include/phmm_amd_mea.h): the legal walk
+        whose states have the largest summed posterior -- run_with_mapping_states with its values kept on the device,
+        exp of them as weights (the Del column times del_weight, InsBegin 0), then run_with_mapping_weighted_path
+        -> (logp_forward[R], score[R], path[total_bases, stride] | None, counts[R, 4], weights[total_entries, 3] | None).
+        At del_weight = 1 the score is the expected number of the path's states, emitting and Del, that the true path
+        shares at the same base; at 0 it counts emitting states only.  The rows are those of run_with_mapping_best_path,
+        so path_states() works on them; weights are the ones used (feeding them to run_with_mapping_weighted_path gives
+        the same bits)."""
+        from . import _ffi_mea
+        L = _ffi.lib()
+        R, te = len(reads), int(L.phmm_mappings_total_entries(mappings._h))
+        stride = int(self.param.n_max_gaps) + 2
+        lf, score = np.empty(R), np.empty(R)
+        counts = np.empty((R, 4), dtype=np.uint32)
+        path = np.empty((reads.total_bases(), stride), dtype=np.uint32) if want_path else None
+        w = np.empty((te, 3)) if want_weights else None
+        _ffi.check(_ffi_mea.lib().phmm_run_with_mapping_mea_path(
+            self._h, reads._h, mappings._h, float(del_weight), _ptr(lf), _ptr(score),
+            _ptr(path) if want_path and path.size else None, _ptr(counts), _ptr(w) if want_weights and te else None))
+        return lf, score, path, counts, w
+
     def run_with_mapping_sample_paths(self, reads: ReadCollection, mappings: Mappings, n_samples: int, seed: int,
                                       want_path: bool = True, want_usage: bool = False):
         """n_samples (1..64) draws from the posterior over paths of every read over its lists, P(path | read, model,

@@ -377,6 +377,51 @@ impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
         out
     }
 
+    /// The maximum-expected-accuracy path of every read over its lists (phmm_run_with_mapping_mea_path,
+    /// include/phmm_amd_mea.h): the legal walk whose states have the largest summed posterior, Del states weighted by
+    /// del_weight (1: emitting and Del states count alike, 0: emitting states only).  Per read the score -- the expected
+    /// number of the path's states that the true path shares at the same base -- and the states in order, Del states
+    /// included, decoded as best_path_with_mapping_amd decodes them.  The reference has no such call.
+    /// Unverified, like the rest of this shim: it has not been compiled here.
+    pub fn mea_path_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings, del_weight: f64) -> Vec<(f64, Vec<State>)> {
+        let m = AmdModel::new(self);
+        let mp = AmdMappings::from_mappings(reads, mappings);
+        let stride = self.param.n_max_gaps + 2;
+        let n_bases: usize = (0..mappings.n_reads()).map(|i| mappings[i].len()).sum();
+        let mut score = vec![0f64; mappings.n_reads().max(1)];
+        let mut path = vec![PHMM_PATH_NONE; (stride * n_bases).max(1)];
+        check(unsafe {
+            phmm_run_with_mapping_mea_path(m.0, reads.h, mp.0, del_weight, ptr::null_mut(), score.as_mut_ptr(),
+                                           path.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())
+        });
+        let mut g = 0usize;  // global base: the order from_mappings wrote
+        let mut out = Vec::with_capacity(mappings.n_reads());
+        for i in 0..mappings.n_reads() {
+            let mapping: &Mapping = &mappings[i];
+            let mut states = Vec::new();
+            for j in 0..mapping.len() {
+                for &code in &path[stride * g..stride * (g + 1)] {
+                    if code == PHMM_PATH_NONE {
+                        break;
+                    }
+                    states.push(if code == PHMM_PATH_INS_BEGIN {
+                        State::InsBegin
+                    } else {
+                        let v = mapping.nodes[j][(code >> 2) as usize];
+                        match code & 3 {
+                            0 => State::Match(v),
+                            1 => State::Ins(v),
+                            _ => State::Del(v),
+                        }
+                    });
+                }
+                g += 1;
+            }
+            out.push((score[i], states));
+        }
+        out
+    }
+
     /// n_samples (1..=64) draws from the posterior over paths of every read over its lists
     /// (phmm_run_with_mapping_sample_paths, include/phmm_amd_sample.h): the forward sums as the filter and one random
     /// walk back per sample.  Per read the forward total over its lists and, per sample, the probability of the sampled

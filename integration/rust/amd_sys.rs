@@ -196,6 +196,14 @@ extern "C" {
                                   run_node: *mut u32, run_len: *mut u32) -> c_int;
     pub fn phmm_alignments_destroy(a: *mut phmm_alignments);
 
+    // (include/phmm_amd_mea.h, the seventh companion header)
+    pub fn phmm_run_with_mapping_weighted_path(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                               weights: *const f64, ib_weight: *const f64, out_score: *mut f64,
+                                               out_path: *mut u32, out_counts: *mut u32) -> c_int;
+    pub fn phmm_run_with_mapping_mea_path(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                          del_weight: f64, out_logp_forward: *mut f64, out_score: *mut f64,
+                                          out_path: *mut u32, out_counts: *mut u32, out_weights: *mut f64) -> c_int;
+
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
     // (include/phmm_amd_share.h, the third companion header)
