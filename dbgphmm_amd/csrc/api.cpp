@@ -1067,6 +1067,16 @@ int phmm_run_with_mapping_mea_path(phmm_model *m, const phmm_reads *reads, const
     });
 }
 
+int phmm_run_with_mapping_tables(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_lf,
+                                 double *out_lb, double *out_f, double *out_fs, double *out_b, double *out_bs) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        check_mapping_nodes(m, mp, reads);
+        if (reads->R == 0) return;
+        run_with_mapping_tables(m, reads, mp, out_lf, out_lb, out_f, out_fs, out_b, out_bs);
+    });
+}
+
 int phmm_run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
                                        uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_path,
                                        uint32_t *out_counts, uint32_t *out_node_usage) {

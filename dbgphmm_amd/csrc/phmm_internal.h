@@ -18,6 +18,7 @@
 #include "../../include/phmm_amd_generate.h"
 #include "../../include/phmm_amd_align.h"
 #include "../../include/phmm_amd_mea.h"
+#include "../../include/phmm_amd_tables.h"
 
 namespace phmm {
 
@@ -544,6 +545,9 @@ void run_with_mapping_weighted_path(phmm_model *m, const phmm_reads *reads, cons
 void run_with_mapping_mea_path(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double del_weight,
                                double *out_lf, double *out_score, uint32_t *out_path, uint32_t *out_counts,
                                double *out_weights, RowSink *sink = nullptr);
+// the forward and the backward table of every read over its lists, per entry and per base (list_tables.hip)
+void run_with_mapping_tables(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_lf, double *out_lb,
+                             double *out_f, double *out_fs, double *out_b, double *out_bs);
 // n_samples draws from the posterior over paths of every read over its lists (sample_paths.hip)
 void run_with_mapping_sample_paths(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_samples,
                                    uint64_t seed, double *out_logp, double *out_path_logp, uint32_t *out_path,

@@ -158,6 +158,139 @@ class DenseTables:
         return self.scal[:, 2]
 
 
+class ListTables:
+    """The tables of the list pass (PHMMModel.run_with_mapping_tables, include/phmm_amd_tables.h): forward_with_mapping
+    and backward_with_mapping of every read on its lists as the PHMMTables they are, natural logs, -inf = probability 0.
+
+    Read r of length L, position p in 0..L-1, g = read_off[r] + p; entry a in [pos_off[g], pos_off[g+1]), v = nodes[a]:
+      fwd[a] = ln F.tables[p].{m, i, d}[v],  fwd_scal[g] = ln F.tables[p].(ib, e)     (F.tables[p].mb is 0)
+      bwd[a] = ln B.tables[p].{m, i, d}[v],  bwd_scal[g] = ln B.tables[p].(mb, ib)    (B.tables[p].e is 0)
+    bwd is the table on list p, B.tables[p] -- not B.table_merged(p + 1), the one a posterior multiplies F.tables[p]
+    with; table_merged() applies the reference's index rule.  A half that was not asked for is None.  Scalars are
+    handed out as [mb, ib, e], the order of DenseTables.scal."""
+
+    def __init__(self):
+        self.read_off = self.pos_off = self.nodes = None
+        self.fwd = self.fwd_scal = self.bwd = self.bwd_scal = None
+        self.logp_forward = self.logp_backward = None
+        self.p_end, self.n_nodes = 0.0, 0
+
+    @staticmethod
+    def from_arrays(read_off, pos_off, nodes, p_end: float, n_nodes: int, forward=None, forward_scalars=None,
+                    backward=None, backward_scalars=None, logp_forward=None, logp_backward=None) -> "ListTables":
+        """From the arrays of the call (or of any other source of the same tables); needs no GPU.  p_end: ln of the
+        model's end probability and n_nodes: its node count, for b_init.  Totals that are not given are read off the
+        scalars: ln F.tables[L-1].e and ln B.tables[0].mb."""
+        t = ListTables()
+        t.read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        t.pos_off = np.ascontiguousarray(pos_off, dtype=np.uint64)
+        t.nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+        tb, te = int(t.read_off[-1]), int(t.pos_off[-1])
+        if t.pos_off.shape[0] != tb + 1 or t.nodes.shape[0] < te:
+            raise ValueError("pos_off / nodes do not fit read_off")
+
+        def plane(a, rows, cols):
+            if a is None:
+                return None
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (rows, cols):
+                raise ValueError(f"expected shape {(rows, cols)}, got {a.shape}")
+            return a
+
+        t.fwd, t.bwd = plane(forward, te, 3), plane(backward, te, 3)
+        t.fwd_scal, t.bwd_scal = plane(forward_scalars, tb, 2), plane(backward_scalars, tb, 2)
+        t.p_end, t.n_nodes = float(p_end), int(n_nodes)
+        R = t.read_off.shape[0] - 1
+        lens = (t.read_off[1:] - t.read_off[:-1]).astype(np.int64)
+        if logp_forward is None and t.fwd_scal is not None:
+            logp_forward = np.full(R, -np.inf)
+            nz = lens > 0
+            logp_forward[nz] = t.fwd_scal[t.read_off[1:][nz].astype(np.int64) - 1, 1]
+        if logp_backward is None and t.bwd_scal is not None:
+            logp_backward = np.full(R, -np.inf)
+            nz = lens > 0
+            logp_backward[nz] = t.bwd_scal[t.read_off[:-1][nz].astype(np.int64), 0]
+        t.logp_forward = None if logp_forward is None else np.asarray(logp_forward, dtype=np.float64)
+        t.logp_backward = None if logp_backward is None else np.asarray(logp_backward, dtype=np.float64)
+        return t
+
+    def __len__(self) -> int:
+        return self.read_off.shape[0] - 1
+
+    def read_len(self, read: int) -> int:
+        return int(self.read_off[read + 1]) - int(self.read_off[read])
+
+    def _span(self, read: int, pos: int):
+        if not 0 <= pos < self.read_len(read):
+            raise IndexError(f"position {pos} outside read {read}")
+        g = int(self.read_off[read]) + pos
+        return g, int(self.pos_off[g]), int(self.pos_off[g + 1])
+
+    def forward(self, read: int, pos: int):
+        """F.tables[pos] of the read -> (nodes[n], values[n, 3] = ln m, i, d, scalars = ln [mb, ib, e])"""
+        g, a0, a1 = self._span(read, pos)
+        vals = None if self.fwd is None else self.fwd[a0:a1]
+        scal = None if self.fwd_scal is None else np.array([-np.inf, self.fwd_scal[g, 0], self.fwd_scal[g, 1]])
+        return self.nodes[a0:a1], vals, scal
+
+    def backward(self, read: int, pos: int):
+        """B.tables[pos] of the read, the table on list pos -> (nodes[n], values[n, 3], scalars = ln [mb, ib, e])"""
+        g, a0, a1 = self._span(read, pos)
+        vals = None if self.bwd is None else self.bwd[a0:a1]
+        scal = None if self.bwd_scal is None else np.array([self.bwd_scal[g, 0], self.bwd_scal[g, 1], -np.inf])
+        return self.nodes[a0:a1], vals, scal
+
+    def table_merged(self, kind: str, read: int, i: int):
+        """PHMMTables::table_merged (table.rs:414-434) -> (nodes, values, scalars) as forward() / backward().
+        'forward': index 0 is f_init (mb = 1, nothing else), index i >= 1 is F.tables[i - 1].
+        'backward': index i >= L is b_init (p_end in every state of every node, nothing else), index i < L is B.tables[i].
+        The two init tables are built from the parameters."""
+        if kind == "forward":
+            if i == 0:
+                return (np.zeros(0, dtype=np.uint32), np.zeros((0, 3)), np.array([0.0, -np.inf, -np.inf]))
+            return self.forward(read, i - 1)
+        if kind == "backward":
+            if i >= self.read_len(read):
+                return (np.arange(self.n_nodes, dtype=np.uint32), np.full((self.n_nodes, 3), self.p_end),
+                        np.array([-np.inf, -np.inf, -np.inf]))
+            return self.backward(read, i)
+        raise ValueError("kind must be 'forward' or 'backward'")
+
+    def prefix_logp(self, read: int) -> np.ndarray:
+        """ln F.tables[p].e for every base p: the likelihood of the prefix ending at base p"""
+        return self.fwd_scal[int(self.read_off[read]):int(self.read_off[read + 1]), 1]
+
+    def suffix_logp(self, read: int) -> np.ndarray:
+        """ln B.tables[p].mb for every base p: the likelihood of the suffix from base p"""
+        return self.bwd_scal[int(self.read_off[read]):int(self.read_off[read + 1]), 0]
+
+    def ins_begin_posterior(self, read: int) -> np.ndarray:
+        """ln of the posterior that base p was emitted from InsBegin, for every base p of the read:
+        ln F.tables[p].ib + ln B.table_merged(p + 1).ib - ln P -- the ib scalar of to_emit_probs(p + 1).  -inf at the
+        last base (b_init.ib = 0) and everywhere for a read of probability 0."""
+        g0, g1 = int(self.read_off[read]), int(self.read_off[read + 1])
+        out = np.full(g1 - g0, -np.inf)
+        lp = float(self.logp_forward[read]) if g1 > g0 else -np.inf
+        if g1 - g0 > 1 and lp > -np.inf:
+            f, b = self.fwd_scal[g0:g1 - 1, 0], self.bwd_scal[g0 + 1:g1, 1]
+            ok = (f > -np.inf) & (b > -np.inf)
+            out[:-1][ok] = f[ok] + b[ok] - lp
+        return out
+
+    def top_states(self, kind: str, read: int, pos: int, n: int):
+        """The first n entries of PHMMTable::to_states() (table.rs:215-254) of F.tables[pos] / B.tables[pos]: every
+        Match in slot order, then every Ins, then every Del, sorted ascending by value (stable) and reversed -- among
+        equal values Del before Ins before Match and the later slot first -> [(node, 'M' | 'I' | 'D', ln value), ...].
+        This is what to_summary_string_n formats."""
+        if kind not in ("forward", "backward"):
+            raise ValueError("kind must be 'forward' or 'backward'")
+        nodes, vals, _ = self.forward(read, pos) if kind == "forward" else self.backward(read, pos)
+        k = nodes.shape[0]
+        flat = vals.T.reshape(-1)  # Match.., Ins.., Del..
+        order = np.argsort(flat, kind="stable")[::-1][:max(int(n), 0)]
+        return [(int(nodes[j % k]), "MID"[j // k], float(flat[j])) for j in order.tolist()]
+
+
 PATH_NONE = 0xFFFFFFFF       # PHMM_PATH_NONE (include/phmm_amd_path.h)
 PATH_INS_BEGIN = 0xFFFFFFFD  # PHMM_PATH_INS_BEGIN
 
@@ -468,6 +601,32 @@ class PHMMModel:
             self._h, reads._h, mappings._h, float(del_weight), _ptr(lf), _ptr(score),
             _ptr(path) if want_path and path.size else None, _ptr(counts), _ptr(w) if want_weights and te else None))
         return lf, score, path, counts, w
+
+    def run_with_mapping_tables(self, reads: ReadCollection, mappings: Mappings, want_forward: bool = True,
+                                want_backward: bool = True) -> "ListTables":
+        """PHMMModel::forward_with_mapping (forward.rs:51-75) and backward_with_mapping (backward.rs:59-93) of every
+        read on its lists, with the tables themselves returned (include/phmm_amd_tables.h) -> ListTables: per list entry
+        ln m, i, d of F.tables[p] and of B.tables[p], per base ln (ib, e) of F and ln (mb, ib) of B, per read
+        ln F.tables[L-1].e and ln B.tables[0].mb.  A half that is not wanted is not run and its arrays are None.
+        A read of probability 0 on its lists is a result: its values are -inf from where the mass ends."""
+        from . import _ffi_tables
+        L = _ffi.lib()
+        R, tb = len(reads), reads.total_bases()
+        te = int(L.phmm_mappings_total_entries(mappings._h))
+        po, nd, _ = mappings.arrays()
+
+        def half(want):
+            if not want:
+                return None, None, None
+            return np.empty(R), np.empty((te, 3)), np.empty((tb, 2))
+
+        lf, f, fs = half(want_forward)
+        lb, b, bs = half(want_backward)
+        _ffi.check(_ffi_tables.lib().phmm_run_with_mapping_tables(
+            self._h, reads._h, mappings._h, _ptr(lf), _ptr(lb), _ptr(f) if f is not None and te else None,
+            _ptr(fs) if fs is not None and tb else None, _ptr(b) if b is not None and te else None,
+            _ptr(bs) if bs is not None and tb else None))
+        return ListTables.from_arrays(reads.offsets, po, nd, self.param.p_end, self.n_nodes, f, fs, b, bs, lf, lb)
 
     def run_with_mapping_sample_paths(self, reads: ReadCollection, mappings: Mappings, n_samples: int, seed: int,
                                       want_path: bool = True, want_usage: bool = False):

@@ -422,6 +422,58 @@ impl<N: PHMMNode, E: PHMMEdge> PHMMModel<N, E> {
         out
     }
 
+    /// forward_with_mapping (forward.rs:51-75) and backward_with_mapping (backward.rs:59-93) of every read on its lists
+    /// with the tables themselves returned (phmm_run_with_mapping_tables, include/phmm_amd_tables.h): per read the pair
+    /// (forward, backward) of PHMMTables that run_with_mapping builds, each table sparse over the nodes of its list, with
+    /// ib / e (forward) and mb / ib (backward) set and the init tables built from the parameters as f_init / b_init do.
+    /// A read of probability 0 on its lists is a result: its tables hold Prob::zero() from where the mass ends.
+    /// Unverified, like the rest of this shim: it has not been compiled here.
+    pub fn tables_with_mapping_amd(&self, reads: &AmdReads, mappings: &Mappings) -> Vec<(PHMMTables, PHMMTables)> {
+        let m = AmdModel::new(self);
+        let mp = AmdMappings::from_mappings(reads, mappings);
+        let n_bases: usize = (0..mappings.n_reads()).map(|i| mappings[i].len()).sum();
+        let n_entries: usize = (0..mappings.n_reads())
+            .map(|i| (0..mappings[i].len()).map(|j| mappings[i].nodes[j].len()).sum::<usize>())
+            .sum();
+        let mut f = vec![0f64; (3 * n_entries).max(1)];
+        let mut b = vec![0f64; (3 * n_entries).max(1)];
+        let mut fs = vec![0f64; (2 * n_bases).max(1)];
+        let mut bs = vec![0f64; (2 * n_bases).max(1)];
+        check(unsafe {
+            phmm_run_with_mapping_tables(m.0, reads.h, mp.0, ptr::null_mut(), ptr::null_mut(), f.as_mut_ptr(),
+                                         fs.as_mut_ptr(), b.as_mut_ptr(), bs.as_mut_ptr())
+        });
+        let (mut g, mut a) = (0usize, 0usize);  // global base and entry: the order from_mappings wrote
+        let mut out = Vec::with_capacity(mappings.n_reads());
+        for i in 0..mappings.n_reads() {
+            let mapping: &Mapping = &mappings[i];
+            let mut ft = PHMMTables { init_table: self.f_init(false), tables: Vec::new(), kind: PHMMKind::Forward };
+            let mut bt = PHMMTables { init_table: self.b_init(false), tables: Vec::new(), kind: PHMMKind::Backward };
+            for j in 0..mapping.len() {
+                let mut tf = PHMMTable::zero(false, self.n_nodes());
+                let mut tb = PHMMTable::zero(false, self.n_nodes());
+                for &v in mapping.nodes[j].iter() {
+                    tf.m[v] = Prob::from_log_prob(f[3 * a]);
+                    tf.i[v] = Prob::from_log_prob(f[3 * a + 1]);
+                    tf.d[v] = Prob::from_log_prob(f[3 * a + 2]);
+                    tb.m[v] = Prob::from_log_prob(b[3 * a]);
+                    tb.i[v] = Prob::from_log_prob(b[3 * a + 1]);
+                    tb.d[v] = Prob::from_log_prob(b[3 * a + 2]);
+                    a += 1;
+                }
+                tf.ib = Prob::from_log_prob(fs[2 * g]);
+                tf.e = Prob::from_log_prob(fs[2 * g + 1]);
+                tb.mb = Prob::from_log_prob(bs[2 * g]);
+                tb.ib = Prob::from_log_prob(bs[2 * g + 1]);
+                ft.tables.push(tf);
+                bt.tables.push(tb);
+                g += 1;
+            }
+            out.push((ft, bt));
+        }
+        out
+    }
+
     /// n_samples (1..=64) draws from the posterior over paths of every read over its lists
     /// (phmm_run_with_mapping_sample_paths, include/phmm_amd_sample.h): the forward sums as the filter and one random
     /// walk back per sample.  Per read the forward total over its lists and, per sample, the probability of the sampled

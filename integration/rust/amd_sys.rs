@@ -204,6 +204,12 @@ extern "C" {
                                           del_weight: f64, out_logp_forward: *mut f64, out_score: *mut f64,
                                           out_path: *mut u32, out_counts: *mut u32, out_weights: *mut f64) -> c_int;
 
+    // (include/phmm_amd_tables.h, the eighth companion header)
+    pub fn phmm_run_with_mapping_tables(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                        out_logp_forward: *mut f64, out_logp_backward: *mut f64, out_forward: *mut f64,
+                                        out_forward_scalars: *mut f64, out_backward: *mut f64,
+                                        out_backward_scalars: *mut f64) -> c_int;
+
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
     // (include/phmm_amd_share.h, the third companion header)
