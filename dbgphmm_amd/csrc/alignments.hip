@@ -21,17 +21,6 @@ namespace phmm {
 
 namespace {
 
-// b holds at least `need` bytes and still its first `used`
-void grow_keep(DevBuf &b, size_t used, size_t need, hipStream_t s) {
-    if (need <= b.bytes) return;
-    DevBuf nb;
-    nb.reserve(std::max(need, 2 * b.bytes));
-    if (used) HIP_CHECK(hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));  // the old buffer is freed below
-    const size_t n = nb.bytes;
-    b.adopt(nb.detach(), n);
-}
-
 struct AlignSink final : RowSink {
     phmm_model *m;
     const phmm_reads *reads;

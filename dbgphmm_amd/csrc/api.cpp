@@ -1121,6 +1121,59 @@ int phmm_alignments_export(const phmm_alignments *a, uint64_t *op_off, uint32_t 
 
 void phmm_alignments_destroy(phmm_alignments *a) { delete a; }
 
+int phmm_run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_groups,
+                                     const uint64_t *group_off, const uint32_t *group_nodes, double *out_lf,
+                                     double *out_key_usage, phmm_read_usage **out) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        // the groups, as phmm_likelihood_set_groups takes them -> the key of every node
+        const uint32_t N = m->N, G = n_groups, NONE = PHMM_GROUP_MIXED;
+        std::vector<uint32_t> key_of;
+        if (G) {
+            if (G == NONE) PHMM_THROW(PHMM_EINVAL, "too many groups");
+            if (!group_off) PHMM_THROW(PHMM_EINVAL, "NULL group_off");
+            if (group_off[0] != 0) PHMM_THROW(PHMM_EINVAL, "group_off[0] must be 0");
+            for (uint32_t g = 0; g < G; g++)
+                if (group_off[g + 1] < group_off[g]) PHMM_THROW(PHMM_EINVAL, "group_off decreases");
+            if (group_off[G] > N) PHMM_THROW(PHMM_EINVAL, "more group entries than nodes: a node is in two groups");
+            if (group_off[G] && !group_nodes) PHMM_THROW(PHMM_EINVAL, "NULL group_nodes");
+            key_of.assign(N, NONE);
+            for (uint32_t g = 0; g < G; g++)
+                for (uint64_t i = group_off[g]; i < group_off[g + 1]; i++) {
+                    const uint32_t v = group_nodes[i];
+                    if (v >= N) PHMM_THROW(PHMM_EINVAL, "group node out of range");
+                    if (key_of[v] != NONE) PHMM_THROW(PHMM_EINVAL, "node in two groups (or twice in one)");
+                    key_of[v] = g;
+                }
+        }
+        check_mapping_nodes(m, mp, reads);
+        std::unique_ptr<phmm_read_usage> h(out ? new phmm_read_usage() : nullptr);
+        if (h) {
+            h->device = m->pool->device;
+            h->K = G ? G : N;
+        }
+        if (reads->R)
+            run_with_mapping_read_usage(m, reads, mp, G ? G : N, G ? key_of.data() : nullptr, out_lf, out_key_usage, h.get());
+        if (out) *out = h.release();  // (a refusal has thrown: *out stays as it was)
+    });
+}
+
+uint64_t phmm_read_usage_reads(const phmm_read_usage *u) { return u ? u->R : 0; }
+uint64_t phmm_read_usage_keys(const phmm_read_usage *u) { return u ? u->K : 0; }
+uint64_t phmm_read_usage_total(const phmm_read_usage *u) { return u ? u->total : 0; }
+
+int phmm_read_usage_export(const phmm_read_usage *u, uint64_t *row_off, uint32_t *keys, double *usage) {
+    return guarded([&] {
+        if (!u) PHMM_THROW(PHMM_EINVAL, "NULL read usage");
+        int dev = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        if (dev != u->device) PHMM_THROW(PHMM_EINVAL, "the read usage lives on another device (phmm_set_device)");
+        read_usage_export(u, row_off, keys, usage);
+    });
+}
+
+void phmm_read_usage_destroy(phmm_read_usage *u) { delete u; }
+
 int phmm_sample_reads(phmm_model *m, uint64_t first_index, uint64_t n_walks, uint32_t length, uint32_t length_kind,
                       const uint32_t *start_nodes, uint64_t n_start_nodes, uint64_t seed, uint8_t *out_bases,
                       uint32_t *out_len, uint32_t *out_flags, uint32_t *out_history, uint32_t history_cap,

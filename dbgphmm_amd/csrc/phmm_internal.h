@@ -19,6 +19,7 @@
 #include "../../include/phmm_amd_align.h"
 #include "../../include/phmm_amd_mea.h"
 #include "../../include/phmm_amd_tables.h"
+#include "../../include/phmm_amd_usage.h"
 
 namespace phmm {
 
@@ -104,6 +105,16 @@ struct DevBuf {
 };
 // copy device -> (host or device) destination
 void copy_out(void *dst, const void *src_dev, size_t bytes);
+// b holds at least `need` bytes and still its first `used` (the arrays a result handle grows chunk by chunk)
+inline void grow_keep(DevBuf &b, size_t used, size_t need, hipStream_t s) {
+    if (need <= b.bytes) return;
+    DevBuf nb;
+    nb.reserve(need > 2 * b.bytes ? need : 2 * b.bytes);
+    if (used) HIP_CHECK(hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // the old buffer is freed below
+    const size_t n = nb.bytes;
+    b.adopt(nb.detach(), n);
+}
 
 // ---------------------------------------------------------------- per-device workspace pool
 // One set of grow-only buffers per pipeline worker (sparse_dyn.hip runs chunks of read groups concurrently on
@@ -354,6 +365,16 @@ struct phmm_alignments {
     phmm::DevBuf d_ops, d_run_node, d_run_len;  // u32[total_ops], u32[total_runs] twice (grown chunk by chunk)
 };
 
+// The sparse read-by-key matrix of one phmm_run_with_mapping_read_usage call (include/phmm_amd_usage.h), CSR over the
+// reads.  The arrays belong to the handle, not to the device workspace, and the handle borrows nothing.
+struct phmm_read_usage {
+    uint64_t R = 0, K = 0, total = 0;
+    int device = -1;
+    phmm::DevBuf d_row_off;  // u64[R+1]
+    phmm::DevBuf d_keys;     // u32[total]
+    phmm::DevBuf d_usage;    // f64[total][3] (both grown chunk by chunk)
+};
+
 // The sampler's state at one k (MultiDbg::to_likelihood, posterior.rs:247-255, through the greedy search of
 // sample_posterior, posterior.rs:314-417): the current copy-number vector and every read's ln P under it, on the device.
 // The value of read r under the current vector is val[r] + ln(T_at[r] / T): val[r] is what the kernels gave when r was
@@ -558,6 +579,11 @@ void run_with_mapping_alignments(phmm_model *m, const phmm_reads *reads, const p
                                  phmm_alignments *h);
 void alignments_export(const phmm_alignments *h, uint64_t *op_off, uint32_t *ops, uint64_t *run_off, uint32_t *run_node,
                        uint32_t *run_len);
+// per read, how often it used every key (node or node group) by state (read_usage.hip); key_of: [N] the key of the node
+// or 0xffffffff, nullptr = the node itself; h == nullptr: scores and totals only
+void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t K,
+                                 const uint32_t *key_of, double *out_lf, double *out_key_usage, phmm_read_usage *h);
+void read_usage_export(const phmm_read_usage *u, uint64_t *row_off, uint32_t *keys, double *usage);
 // reads drawn from the model, one walk per lane (sample_reads.hip)
 void sample_reads(phmm_model *m, uint64_t first_index, uint64_t n_walks, uint32_t length, uint32_t length_kind,
                   const uint32_t *start_nodes, uint64_t n_start_nodes, uint64_t seed, uint8_t *out_bases, uint32_t *out_len,

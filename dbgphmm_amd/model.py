@@ -392,6 +392,84 @@ class Alignments:
         return out
 
 
+class ReadUsage:
+    """The rows of PHMMModel.run_with_mapping_read_usage (include/phmm_amd_usage.h): per read the distinct keys (nodes,
+    or node groups) among its list entries in ascending order and, per key, the summed posterior of the read's Match,
+    Ins and Del states there -- PHMMOutput::to_state_probs() of the read, kept sparse.  CSR over the reads; the rows
+    stay on the device until arrays() is first called.  totals[K, 3]: the column sums over all reads (None if the call
+    did not ask for them)."""
+
+    def __init__(self, handle, n_reads: int, n_keys: int, totals=None):
+        self._h = handle
+        self.n_reads, self.n_keys = int(n_reads), int(n_keys)
+        self.totals = totals
+        self._cache = None
+        self._by_key = None
+
+    @staticmethod
+    def from_arrays(n_keys: int, row_off, keys, usage, totals=None) -> "ReadUsage":
+        """rows that are on the host already (a file read back, a test)"""
+        row_off = np.asarray(row_off, dtype=np.uint64)
+        u = ReadUsage(None, row_off.shape[0] - 1, n_keys, totals)
+        u._cache = (row_off, np.asarray(keys, dtype=np.uint32), np.asarray(usage, dtype=np.float64).reshape(-1, 3))
+        assert int(row_off[-1]) == u._cache[1].shape[0] == u._cache[2].shape[0]
+        return u
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            from . import _ffi_usage
+            _ffi_usage.lib().phmm_read_usage_destroy(self._h)
+            self._h = None
+
+    def __len__(self) -> int:
+        return self.n_reads
+
+    def arrays(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(row_off[R + 1], keys[total], usage[total, 3]), copied from the device on the first call"""
+        if self._cache is None:
+            from . import _ffi_usage
+            L = _ffi_usage.lib()
+            R, total = int(L.phmm_read_usage_reads(self._h)), int(L.phmm_read_usage_total(self._h))
+            row_off = np.empty(R + 1, dtype=np.uint64)
+            keys, usage = np.empty(max(total, 1), dtype=np.uint32), np.empty((max(total, 1), 3))
+            _ffi.check(L.phmm_read_usage_export(self._h, _ptr(row_off), _ptr(keys), _ptr(usage)))
+            self._cache = (row_off, keys[:total], usage[:total])
+        return self._cache
+
+    def row(self, r: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(keys[n], usage[n, 3]) of read r"""
+        row_off, keys, usage = self.arrays()
+        e0, e1 = int(row_off[r]), int(row_off[r + 1])
+        return keys[e0:e1], usage[e0:e1]
+
+    def state_probs(self, r: int) -> np.ndarray:
+        """dense [K, 3]: to_state_probs() of read r (Match, Ins, Del per key)"""
+        keys, usage = self.row(r)
+        out = np.zeros((self.n_keys, 3))
+        out[keys] = usage
+        return out
+
+    def node_freqs(self, r: int) -> np.ndarray:
+        """dense [K]: the reference's to_node_freqs() of read r, (Match + Ins) + Del per key"""
+        keys, usage = self.row(r)
+        out = np.zeros(self.n_keys)
+        out[keys] = usage[:, 0] + usage[:, 1] + usage[:, 2]
+        return out
+
+    def reads_of(self, key: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(reads[n], usage[n, 3]): the reads whose row holds the key, in ascending order, and their entries -- the
+        transpose of row()"""
+        row_off, keys, usage = self.arrays()
+        if self._by_key is None:
+            read_of = np.repeat(np.arange(self.n_reads, dtype=np.int64), np.diff(row_off.astype(np.int64)))
+            order = np.argsort(keys, kind="stable")
+            self._by_key = (order, keys[order], read_of)
+        order, sorted_keys, read_of = self._by_key
+        e0, e1 = np.searchsorted(sorted_keys, key, side="left"), np.searchsorted(sorted_keys, key, side="right")
+        sel = order[e0:e1]
+        return read_of[sel], usage[sel]
+
+
 class PHMMModel:
     """PHMMModel<N, E> (src/hmmv2/common.rs:61-64) resident on one MI355X."""
 
@@ -670,6 +748,32 @@ class PHMMModel:
             self._h, reads._h, mappings._h, S, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(lp),
             _ptr(plp) if S and plp.size else None, _ptr(counts) if counts.size else None, C.byref(h)))
         return lp, plp, counts, Alignments(h, R, S)
+
+    def run_with_mapping_read_usage(self, reads: ReadCollection, mappings: Mappings, groups=None, want_totals: bool = True):
+        """Per read, how often the read used every node by state over its lists (include/phmm_amd_usage.h):
+        PHMMOutput::to_state_probs() / to_node_freqs() of every read, as a sparse read-by-key matrix reduced on the
+        device from the values of run_with_mapping_states, which never leave it -> (logp_forward[R], ReadUsage).
+        groups = (group_off, group_nodes) as for Likelihood.set_groups: the key of a node is its group, and the entries
+        of a node in no group are left out; None: the key of a node is the node.  want_totals: ReadUsage.totals[K, 3],
+        the column sums over all reads.  Every sum runs in a fixed order, so a read's row depends on the model, the read
+        and its lists alone."""
+        from . import _ffi_usage
+        R = len(reads)
+        n_groups, g_off, g_nodes = 0, None, None
+        if groups is not None:
+            g_off = np.ascontiguousarray(groups[0], dtype=np.uint64).reshape(-1)
+            g_nodes = np.ascontiguousarray(groups[1], dtype=np.uint32).reshape(-1)
+            n_groups = g_off.shape[0] - 1
+            if n_groups < 1:
+                raise ValueError("groups: group_off needs at least two entries")
+        K = n_groups if n_groups else self.n_nodes
+        lf = np.empty(R)
+        totals = np.zeros((K, 3)) if want_totals else None
+        h = C.c_void_p()
+        _ffi.check(_ffi_usage.lib().phmm_run_with_mapping_read_usage(
+            self._h, reads._h, mappings._h, n_groups, _ptr(g_off), _ptr(g_nodes) if n_groups and g_nodes.size else None,
+            _ptr(lf), _ptr(totals) if want_totals and R else None, C.byref(h)))
+        return lf, ReadUsage(h, R, K, totals)
 
     _GEN_KINDS = {"state_count": 0, "endable": 1, "emit_count": 2}
 

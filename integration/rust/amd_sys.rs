@@ -64,6 +64,10 @@ pub struct phmm_likelihood {
 pub struct phmm_alignments {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct phmm_read_usage {
+    _p: [u8; 0],
+}
 
 #[link(name = "phmm_amd")]
 /// phmm_likelihood_current_groups: a node-form move changed part of the group
@@ -209,6 +213,17 @@ extern "C" {
                                         out_logp_forward: *mut f64, out_logp_backward: *mut f64, out_forward: *mut f64,
                                         out_forward_scalars: *mut f64, out_backward: *mut f64,
                                         out_backward_scalars: *mut f64) -> c_int;
+
+    // (include/phmm_amd_usage.h, the ninth companion header; phmm_read_usage is an opaque handle like phmm_alignments)
+    pub fn phmm_run_with_mapping_read_usage(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                            n_groups: u32, group_off: *const u64, group_nodes: *const u32,
+                                            out_logp_forward: *mut f64, out_key_usage: *mut f64,
+                                            out: *mut *mut phmm_read_usage) -> c_int;
+    pub fn phmm_read_usage_reads(u: *const phmm_read_usage) -> u64;
+    pub fn phmm_read_usage_keys(u: *const phmm_read_usage) -> u64;
+    pub fn phmm_read_usage_total(u: *const phmm_read_usage) -> u64;
+    pub fn phmm_read_usage_export(u: *const phmm_read_usage, row_off: *mut u64, keys: *mut u32, usage: *mut f64) -> c_int;
+    pub fn phmm_read_usage_destroy(u: *mut phmm_read_usage);
 
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
