@@ -1174,6 +1174,52 @@ int phmm_read_usage_export(const phmm_read_usage *u, uint64_t *row_off, uint32_t
 
 void phmm_read_usage_destroy(phmm_read_usage *u) { delete u; }
 
+int phmm_run_with_mapping_read_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_keys,
+                                     const uint32_t *edge_key, const uint32_t *init_key, double *out_lf,
+                                     double *out_end_terms, double *out_key_usage, phmm_read_edges **out) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        const uint32_t N = m->N, E = m->E;
+        if (n_keys) {
+            if (n_keys == PHMM_NO_KEY) PHMM_THROW(PHMM_EINVAL, "too many keys");
+            if (!edge_key && !init_key) PHMM_THROW(PHMM_EINVAL, "n_keys > 0 with edge_key and init_key both NULL");
+            for (uint32_t e = 0; edge_key && e < E; e++)
+                if (edge_key[e] >= n_keys && edge_key[e] != PHMM_NO_KEY) PHMM_THROW(PHMM_EINVAL, "edge_key value out of range");
+            for (uint32_t v = 0; init_key && v < N; v++)
+                if (init_key[v] >= n_keys && init_key[v] != PHMM_NO_KEY) PHMM_THROW(PHMM_EINVAL, "init_key value out of range");
+        } else if ((uint64_t)E + N >= PHMM_NO_KEY) {
+            PHMM_THROW(PHMM_ECAPACITY, "E + N does not fit the key space");
+        }
+        const uint32_t K = n_keys ? n_keys : E + N;
+        check_mapping_nodes(m, mp, reads);
+        std::unique_ptr<phmm_read_edges> h(out ? new phmm_read_edges() : nullptr);
+        if (h) {
+            h->device = m->pool->device;
+            h->K = K;
+        }
+        if (reads->R)
+            run_with_mapping_read_edges(m, reads, mp, K, n_keys != 0, edge_key, init_key, out_lf, out_end_terms,
+                                        out_key_usage, h.get());
+        if (out) *out = h.release();  // (a refusal has thrown: *out stays as it was)
+    });
+}
+
+uint64_t phmm_read_edges_reads(const phmm_read_edges *u) { return u ? u->R : 0; }
+uint64_t phmm_read_edges_keys(const phmm_read_edges *u) { return u ? u->K : 0; }
+uint64_t phmm_read_edges_total(const phmm_read_edges *u) { return u ? u->total : 0; }
+
+int phmm_read_edges_export(const phmm_read_edges *u, uint64_t *row_off, uint32_t *keys, double *usage) {
+    return guarded([&] {
+        if (!u) PHMM_THROW(PHMM_EINVAL, "NULL read edges");
+        int dev = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        if (dev != u->device) PHMM_THROW(PHMM_EINVAL, "the read edges live on another device (phmm_set_device)");
+        read_edges_export(u, row_off, keys, usage);
+    });
+}
+
+void phmm_read_edges_destroy(phmm_read_edges *u) { delete u; }
+
 int phmm_sample_reads(phmm_model *m, uint64_t first_index, uint64_t n_walks, uint32_t length, uint32_t length_kind,
                       const uint32_t *start_nodes, uint64_t n_start_nodes, uint64_t seed, uint8_t *out_bases,
                       uint32_t *out_len, uint32_t *out_flags, uint32_t *out_history, uint32_t history_cap,

@@ -2019,26 +2019,25 @@ __global__ void __launch_bounds__(BLOCK) init_end_terms(const double *init, cons
     freq[v] += init[v] * (A + mt);
 }
 
-// PHMMModel::run_with_mapping (freq.rs:72-76) of every read on its lists, then PHMMOutput::to_edge_and_init_freqs
-// (freq.rs:276-298, 332-389) summed over the reads.  The list pass (sparse_backward_kernel<CAP, true>) holds at step pos
-// the three columns merged index pos reads: F.tables[pos-1], B.tables[pos] and B.tables[pos+1].  It writes the nonzero
-// terms of that index into the record of position pos (index len into that of len-1); the records are compacted in
-// position order, sorted by key (stable) and summed one wave per key, as Mappings::to_node_freqs: the same bits
-// whatever the timing.  The terms over b_init's every node come from two scalars per read.
-void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
-                            double *out_ef, double *out_if) {
+// The adaptive flow plans its memory as if every byte the pool holds were its own to reuse (planned_budget): the record
+// slots and sort buffers of the two edge calls, gigabytes on a repeat, go back when the call ends.
+EdgeScratchRelease::~EdgeScratchRelease() {
+    for (int i : {5, 6, 13, 14, 16, 17, 18, 19, 20, 21}) m->wset().aux[i].release();
+}
+
+// The front half of run_with_mapping_edges and run_with_mapping_read_edges (read_edges.hip): setup, record bounds, the
+// class split, the list kernels with the opt-in block path, the error check and the compaction in position order.  It
+// leaves the compacted (key, value) records and their per-position offsets on the device (workspace buffers 18, 19 and
+// 13: the caller holds an EdgeScratchRelease) and ln P of every read on the host.
+// The list pass (sparse_backward_kernel<CAP, true>) holds at step pos the three columns merged index pos reads:
+// F.tables[pos-1], B.tables[pos] and B.tables[pos+1].  It writes the nonzero terms of that index into the record of
+// position pos (index len into that of len-1).  The terms over b_init's every node are not records: they come from two
+// scalars per read (edge_end_terms).
+void edge_list_records(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, EdgeRecords &er) {
     hipStream_t s = current_stream();
     const uint64_t R = reads->R, n_pos = reads->total;
     const uint32_t N = m->N, E = m->E;
-    // The adaptive flow plans its memory as if every byte the pool holds were its own to reuse (planned_budget): the
-    // record slots and sort buffers of this call, gigabytes on a repeat, go back when it ends.
-    struct ReleaseScratch {
-        phmm_model *m;
-        ~ReleaseScratch() {
-            for (int i : {5, 6, 13, 14, 16, 17, 18, 19, 20, 21}) m->wset().aux[i].release();
-        }
-    } release_scratch{m};
-    std::vector<double> lf;
+    std::vector<double> &lf = er.lf;
     SparseBwdEdgeArgs ba{};
     std::vector<uint32_t> cls[2];
     unsigned long long *d_cells = nullptr;
@@ -2118,19 +2117,59 @@ void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_m
     HIP_CHECK(hipMemcpyAsync(&total, d_coff.as<uint64_t>() + n_pos, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     const uint64_t nt = std::max<uint64_t>(total, 1);
-    DevBuf &d_ck = m->wset().aux[18], &d_cv = m->wset().aux[19], &d_sk = m->wset().aux[20], &d_sv = m->wset().aux[21],
-           &d_freq = m->wset().aux[16];
+    DevBuf &d_ck = m->wset().aux[18], &d_cv = m->wset().aux[19];
     d_ck.reserve(sizeof(uint32_t) * nt);
     d_cv.reserve(sizeof(double) * nt);
+    if (total) {
+        hipLaunchKernelGGL(edge_rec_compact, dim3((unsigned)((n_pos + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, rec_off,
+                           rec_cnt, d_coff.as<uint64_t>(), n_pos, ba.rec_key, ba.rec_val, d_ck.as<uint32_t>(),
+                           d_cv.as<double>());
+        HIP_CHECK(hipGetLastError());
+    }
+    er.total = total;
+    er.key = d_ck.as<uint32_t>();
+    er.val = d_cv.as<double>();
+    er.pos_off = d_coff.as<uint64_t>();
+    er.logib = ba.M.logib;
+    er.init = ba.M.init;
+    er.emis = ba.M.emis;
+}
+
+// b_init's Begin terms of read r (table.rs:414-434: B.table_merged(len) has m = d = p_end on every node):
+//   index len-1, to Match: c_M(len-1) ib_{len-2} init_v e_v(x[len-1]) p_end / P  -> T_r e_v(x[len-1])
+//   index len,   to Del:   p_ID ib_{len-1} init_v p_end / P                      -> A_r
+// (c_M(0) = p_MM with mb = 1 for a read of one base, ib chain in the exponent as in the kernel)
+void edge_end_terms(const phmm_model *m, const phmm_reads *reads, const std::vector<double> &lf,
+                    const std::vector<double> &logib, uint64_t r, double &A_r, double &T_r) {
+    const LinParams &lp = m->lin;
+    const uint64_t len = reads->off[r + 1] - reads->off[r];
+    const double libM = len == 1 ? 0.0 : logib[len - 2];
+    const double cM = len == 1 ? lp.p_MM : lp.p_IM;
+    T_r = cM * lp.p_end * std::exp(libM - lf[r]);
+    A_r = lp.p_ID * lp.p_end * std::exp(logib[len - 1] - lf[r]);
+}
+
+// PHMMModel::run_with_mapping (freq.rs:72-76) of every read on its lists, then PHMMOutput::to_edge_and_init_freqs
+// (freq.rs:276-298, 332-389) summed over the reads: the records of edge_list_records sorted by key (stable) and summed
+// one wave per key, then the end terms.
+void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
+                            double *out_ef, double *out_if) {
+    hipStream_t s = current_stream();
+    const uint64_t R = reads->R;
+    const uint32_t N = m->N, E = m->E;
+    EdgeScratchRelease release_scratch{m};
+    EdgeRecords er;
+    edge_list_records(m, reads, mp_in, er);
+    const std::vector<double> &lf = er.lf;
+    const uint64_t total = er.total, nt = std::max<uint64_t>(total, 1);
+    DevBuf &d_ck = m->wset().aux[18], &d_cv = m->wset().aux[19], &d_sk = m->wset().aux[20], &d_sv = m->wset().aux[21],
+           &d_freq = m->wset().aux[16], &d_tmp = m->wset().aux[14];
     d_sk.reserve(sizeof(uint32_t) * nt);
     d_sv.reserve(sizeof(double) * nt);
     const uint32_t K = E + N;
     d_freq.reserve(sizeof(double) * K + 256 * (sizeof(double) + 1) + 256);
     double *freq = d_freq.as<double>();
     if (total) {
-        hipLaunchKernelGGL(edge_rec_compact, dim3((unsigned)((n_pos + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, rec_off,
-                           rec_cnt, d_coff.as<uint64_t>(), n_pos, ba.rec_key, ba.rec_val, d_ck.as<uint32_t>(),
-                           d_cv.as<double>());
         int end_bit = 1;
         while (end_bit < 32 && (1ull << end_bit) < K) end_bit++;
         size_t sb = 0;
@@ -2143,24 +2182,20 @@ void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_m
     hipLaunchKernelGGL(map_node_freq, dim3((K + NODE_FREQ_WAVES - 1) / NODE_FREQ_WAVES), dim3(64 * NODE_FREQ_WAVES), 0, s,
                        d_sk.as<uint32_t>(), d_sv.as<double>(), total, K, freq);
     HIP_CHECK(hipGetLastError());
-    // b_init's Begin terms (table.rs:414-434: B.table_merged(len) has m = d = p_end on every node):
-    //   index len-1, to Match: c_M(len-1) ib_{len-2} init_v e_v(x[len-1]) p_end / P  -> T[x[len-1]]
-    //   index len,   to Del:   p_ID ib_{len-1} init_v p_end / P                      -> A
-    // (c_M(0) = p_MM with mb = 1 for a read of one base, ib chain in the exponent as in the kernel)
+    // b_init's Begin terms (edge_end_terms), summed over the reads per last base: T[x[len-1]] and A
     {
         std::vector<double> logib(std::max<uint64_t>(reads->max_len, 1));
-        HIP_CHECK(hipMemcpy(logib.data(), ba.M.logib, sizeof(double) * logib.size(), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(logib.data(), er.logib, sizeof(double) * logib.size(), hipMemcpyDeviceToHost));
         const LinParams &lp = m->lin;
         double A = 0.0, T[256] = {0.0};
         bool seen[256] = {false};
         for (uint64_t r = 0; r < R; r++) {
-            const uint64_t len = reads->off[r + 1] - reads->off[r];
             const uint8_t xl = reads->bases[reads->off[r + 1] - 1];
-            const double libM = len == 1 ? 0.0 : logib[len - 2];
-            const double cM = len == 1 ? lp.p_MM : lp.p_IM;
-            T[xl] += cM * lp.p_end * std::exp(libM - lf[r]);
+            double A_r, T_r;
+            edge_end_terms(m, reads, lf, logib, r, A_r, T_r);
+            T[xl] += T_r;
             seen[xl] = true;
-            A += lp.p_ID * lp.p_end * std::exp(logib[len - 1] - lf[r]);
+            A += A_r;
         }
         std::vector<uint8_t> letters;
         std::vector<double> tv;
@@ -2173,7 +2208,7 @@ void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_m
         uint8_t *d_letters = (uint8_t *)(d_T + 256);
         HIP_CHECK(hipMemcpyAsync(d_T, tv.data(), sizeof(double) * tv.size(), hipMemcpyHostToDevice, s));
         HIP_CHECK(hipMemcpyAsync(d_letters, letters.data(), letters.size(), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(init_end_terms, dim3((N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, ba.M.init, ba.M.emis, N, lp, A,
+        hipLaunchKernelGGL(init_end_terms, dim3((N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, er.init, er.emis, N, lp, A,
                            (const uint8_t *)d_letters, (const double *)d_T, (int)letters.size(), freq + E);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));  // (host arrays above)

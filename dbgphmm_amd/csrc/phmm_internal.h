@@ -20,6 +20,7 @@
 #include "../../include/phmm_amd_mea.h"
 #include "../../include/phmm_amd_tables.h"
 #include "../../include/phmm_amd_usage.h"
+#include "../../include/phmm_amd_edges.h"
 
 namespace phmm {
 
@@ -375,6 +376,16 @@ struct phmm_read_usage {
     phmm::DevBuf d_usage;    // f64[total][3] (both grown chunk by chunk)
 };
 
+// The sparse read-by-key matrix of one phmm_run_with_mapping_read_edges call (include/phmm_amd_edges.h), CSR over the
+// reads.  The arrays belong to the handle, not to the device workspace, and the handle borrows nothing.
+struct phmm_read_edges {
+    uint64_t R = 0, K = 0, total = 0;
+    int device = -1;
+    phmm::DevBuf d_row_off;  // u64[R+1]
+    phmm::DevBuf d_keys;     // u32[total]
+    phmm::DevBuf d_usage;    // f64[total]
+};
+
 // The sampler's state at one k (MultiDbg::to_likelihood, posterior.rs:247-255, through the greedy search of
 // sample_posterior, posterior.rs:314-417): the current copy-number vector and every read's ln P under it, on the device.
 // The value of read r under the current vector is val[r] + ln(T_at[r] / T): val[r] is what the kernels gave when r was
@@ -548,6 +559,34 @@ void run_with_mapping_edges(phmm_model *m, const phmm_reads *reads, const phmm_m
                             double *out_ef, double *out_if);
 void run_with_mapping_states(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, double *out_lf,
                              double *out_state_logp, uint32_t *out_best);
+// The front half of the two edge calls (mapping_flow.hip): the edge-term list pass of every read and its records,
+// compacted in position order.  The device arrays are workspace buffers; an EdgeScratchRelease in the caller gives them
+// (and the caller's own sort buffers) back when the call ends.
+struct EdgeRecords {
+    std::vector<double> lf;             // [R] ln P of every read
+    uint64_t total = 0;                 // records
+    const uint32_t *key = nullptr;      // device [total]: the edge id, or E + v for Begin -> v
+    const double *val = nullptr;        // device [total]
+    const uint64_t *pos_off = nullptr;  // device [n_pos + 1]: the first record of every read position
+    const double *logib = nullptr;      // device: the model's ib chain, logs
+    const double *init = nullptr;       // device [N]
+    const uint8_t *emis = nullptr;      // device [N]
+};
+struct EdgeScratchRelease {
+    phmm_model *m;
+    ~EdgeScratchRelease();
+};
+void edge_list_records(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp_in, EdgeRecords &er);
+// the two scalars of read r behind its Begin terms at its last base; logib: host copy of EdgeRecords::logib
+void edge_end_terms(const phmm_model *m, const phmm_reads *reads, const std::vector<double> &lf,
+                    const std::vector<double> &logib, uint64_t r, double &A_r, double &T_r);
+// per read, how often it crossed every key (edge, Begin transition or a caller's group of them) (read_edges.hip);
+// edge_key [E] / init_key [N]: the key or 0xffffffff, host arrays, nullptr with K == E + N = the default keys, else
+// that kind left out; h == nullptr: scores and totals only
+void run_with_mapping_read_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t K, bool mapped,
+                                 const uint32_t *edge_key, const uint32_t *init_key, double *out_lf, double *out_end_terms,
+                                 double *out_key_usage, phmm_read_edges *h);
+void read_edges_export(const phmm_read_edges *u, uint64_t *row_off, uint32_t *keys, double *usage);
 // A device consumer of the rows of the two calls below (alignments.hip).  With a sink every chunk's rows are staged in
 // the workspace, as for a host out_path, and handed over on the call's stream behind the walk in place of the copy out.
 struct RowSink {

@@ -20,6 +20,8 @@
 //                    map_node_freq (mapping_flow.hip) does it -- lane-strided partial sums in read order, then the
 //                    butterfly above.
 // No floating-point atomics anywhere; nothing depends on which wave runs first.
+// The kernels have internal linkage: read_edges_kernel.h uses ru_heads, ru_seg_starts, ru_row_off and ru_iota from a
+// second translation unit.
 #pragma once
 
 #include "phmm_internal.h"
@@ -32,16 +34,16 @@ static constexpr uint32_t RU_LANE_MAX = 64;  // longest segment a single lane su
 static constexpr int RU_WAVES = 4;           // waves per block of the two reduction kernels
 
 // first entry of every read: ent[r] = pos_off[read_off[r]], r = 0..R
-__global__ void __launch_bounds__(256) ru_entry_offsets(const uint64_t *read_off, const uint64_t *pos_off, uint64_t R,
-                                                        uint64_t *ent) {
+static __global__ void __launch_bounds__(256) ru_entry_offsets(const uint64_t *read_off, const uint64_t *pos_off, uint64_t R,
+                                                               uint64_t *ent) {
     const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (r <= R) ent[r] = pos_off[read_off[r]];
 }
 
 // ent: the offsets above; r0, r1: the reads of the chunk; key_of: [N] group of the node or RU_NONE, null = the node itself
-__global__ void __launch_bounds__(256) ru_sort_keys(const uint64_t *ent, uint32_t r0, uint32_t r1, const uint32_t *nodes,
-                                                    const uint32_t *key_of, uint32_t key_bits, uint32_t n, uint64_t *keys,
-                                                    uint32_t *vals) {
+static __global__ void __launch_bounds__(256) ru_sort_keys(const uint64_t *ent, uint32_t r0, uint32_t r1, const uint32_t *nodes,
+                                                           const uint32_t *key_of, uint32_t key_bits, uint32_t n, uint64_t *keys,
+                                                           uint32_t *vals) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const uint64_t a = ent[r0] + i;
@@ -56,14 +58,14 @@ __global__ void __launch_bounds__(256) ru_sort_keys(const uint64_t *ent, uint32_
     vals[i] = i;
 }
 
-__global__ void __launch_bounds__(256) ru_heads(const uint64_t *keys, uint32_t n, uint32_t *head) {
+static __global__ void __launch_bounds__(256) ru_heads(const uint64_t *keys, uint32_t n, uint32_t *head) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) head[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
 }
 
 // seg_incl: the inclusive scan of the heads; seg_start[S] = n closes the last segment
-__global__ void __launch_bounds__(256) ru_seg_starts(const uint64_t *keys, const uint32_t *seg_incl, uint32_t n,
-                                                     uint32_t *seg_start) {
+static __global__ void __launch_bounds__(256) ru_seg_starts(const uint64_t *keys, const uint32_t *seg_incl, uint32_t n,
+                                                            uint32_t *seg_start) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     if (i == 0 || keys[i] != keys[i - 1]) seg_start[seg_incl[i] - 1] = i;
@@ -72,8 +74,8 @@ __global__ void __launch_bounds__(256) ru_seg_starts(const uint64_t *keys, const
 
 // row_off[r] = rows_done + the first of the chunk's S segments whose read is >= r - r0, for r = r0 .. r1 (r1 gets
 // rows_done + S: the next chunk overwrites it with the same value)
-__global__ void __launch_bounds__(256) ru_row_off(const uint64_t *keys, const uint32_t *seg_start, uint32_t S, uint32_t r0,
-                                                  uint32_t r1, uint32_t key_bits, uint64_t rows_done, uint64_t *row_off) {
+static __global__ void __launch_bounds__(256) ru_row_off(const uint64_t *keys, const uint32_t *seg_start, uint32_t S, uint32_t r0,
+                                                         uint32_t r1, uint32_t key_bits, uint64_t rows_done, uint64_t *row_off) {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j > r1 - r0) return;
     uint32_t lo = 0, hi = S;
@@ -94,9 +96,9 @@ __device__ __forceinline__ double ru_butterfly(double v) {
 
 // plane: [total_entries][3] logs; ent0: the first entry of the chunk; S segments (the RU_NO_KEY one is not among them)
 // out_keys / out_usage: the handle's arrays at the chunk's first row entry
-__global__ void __launch_bounds__(64 * RU_WAVES) ru_reduce(const double *plane, uint64_t ent0, const uint64_t *keys,
-                                                           const uint32_t *vals, const uint32_t *seg_start, uint32_t S,
-                                                           uint32_t key_mask, uint32_t *out_keys, double *out_usage) {
+static __global__ void __launch_bounds__(64 * RU_WAVES) ru_reduce(const double *plane, uint64_t ent0, const uint64_t *keys,
+                                                                  const uint32_t *vals, const uint32_t *seg_start, uint32_t S,
+                                                                  uint32_t key_mask, uint32_t *out_keys, double *out_usage) {
     const int lane = threadIdx.x & 63;
     const uint32_t base = (blockIdx.x * RU_WAVES + (threadIdx.x >> 6)) * 64;
     if (base >= S) return;  // (a whole wave)
@@ -146,8 +148,8 @@ __global__ void __launch_bounds__(64 * RU_WAVES) ru_reduce(const double *plane, 
 
 // the column totals: sorted_keys / sorted_rows are the T row entries of all reads, stably sorted by key (so in read
 // order within a key); usage is the handle's [T][3]; totals [K][3]
-__global__ void __launch_bounds__(64 * RU_WAVES) ru_col_sum(const uint32_t *sorted_keys, const uint32_t *sorted_rows,
-                                                            uint32_t T, const double *usage, uint32_t K, double *totals) {
+static __global__ void __launch_bounds__(64 * RU_WAVES) ru_col_sum(const uint32_t *sorted_keys, const uint32_t *sorted_rows,
+                                                                   uint32_t T, const double *usage, uint32_t K, double *totals) {
     const uint32_t k = blockIdx.x * RU_WAVES + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (k >= K) return;  // (a whole wave)
@@ -180,7 +182,7 @@ __global__ void __launch_bounds__(64 * RU_WAVES) ru_col_sum(const uint32_t *sort
     }
 }
 
-__global__ void __launch_bounds__(256) ru_iota(uint32_t n, uint32_t *v) {
+static __global__ void __launch_bounds__(256) ru_iota(uint32_t n, uint32_t *v) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) v[i] = i;
 }

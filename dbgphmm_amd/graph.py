@@ -255,6 +255,34 @@ def unitig_groups(sg: SeqGraph) -> Tuple[np.ndarray, np.ndarray]:
     return np.array(off, dtype=np.uint64), nodes
 
 
+PHMM_NO_KEY = 0xFFFFFFFF  # include/phmm_amd_edges.h: the term has no key and is left out
+
+
+def link_keys(arrays, groups) -> Tuple[np.ndarray, np.ndarray]:
+    """The edge map of PHMMModel.run_with_mapping_read_edges that asks "which junctions between node groups did the
+    read cross": groups = (group_off, group_nodes) as Likelihood.set_groups takes them (disjoint; a node may be in no
+    group), arrays anything with edge_src / edge_dst (PHMMArrays, SeqGraph).  Every edge whose two ends lie in two
+    different groups gets the index of its ordered pair (g_src, g_dst), equal pairs sharing one key; every other edge
+    -- inside a group, or with an end in no group -- gets PHMM_NO_KEY.  The pairs are numbered in ascending order of
+    (g_src, g_dst).  -> (edge_key[E] uint32, links[K, 2] int64).  Fed to the call with init_key=None and n_keys=K (K > 0),
+    row r holds the links read r crossed and how often."""
+    g_off = np.asarray(groups[0], dtype=np.int64).reshape(-1)
+    g_nodes = np.asarray(groups[1], dtype=np.int64).reshape(-1)
+    src, dst = np.asarray(arrays.edge_src, dtype=np.int64), np.asarray(arrays.edge_dst, dtype=np.int64)
+    n = int(max(src.max(initial=-1), dst.max(initial=-1), g_nodes.max(initial=-1))) + 1
+    n = max(n, int(getattr(arrays, "n_nodes", 0) or 0))
+    g_of = np.full(n, -1, dtype=np.int64)
+    g_of[g_nodes] = np.repeat(np.arange(g_off.shape[0] - 1, dtype=np.int64), np.diff(g_off))
+    gs, gd = g_of[src], g_of[dst]
+    cross = (gs >= 0) & (gd >= 0) & (gs != gd)
+    pairs = np.stack([gs[cross], gd[cross]], axis=1)
+    links, inv = (np.unique(pairs, axis=0, return_inverse=True) if pairs.shape[0]
+                  else (np.zeros((0, 2), dtype=np.int64), np.zeros(0, dtype=np.int64)))
+    edge_key = np.full(src.shape[0], PHMM_NO_KEY, dtype=np.uint32)
+    edge_key[cross] = np.asarray(inv, dtype=np.int64).reshape(-1)
+    return edge_key, links.astype(np.int64).reshape(-1, 2)
+
+
 # ---------------------------------------------------------------- synthetic genomes / DBG
 
 _B = np.uint64(0x9E3779B97F4A7C15)  # odd multiplier for the rolling hash

@@ -8,6 +8,7 @@ libphmm_amd.so (HIP, gfx950); this module only marshals arrays.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -470,6 +471,104 @@ class ReadUsage:
         return read_of[sel], usage[sel]
 
 
+class ReadEdges:
+    """The rows of PHMMModel.run_with_mapping_read_edges (include/phmm_amd_edges.h): per read the distinct keys (edges and
+    Begin transitions, or the keys of the caller's map) among the nonzero transition terms of the read in ascending
+    order and, per key, their sum -- PHMMOutput::to_edge_and_init_freqs() of the read, kept sparse.  A key absent from a
+    row counts as 0.  CSR over the reads; the rows stay on the device until arrays() is first called.  totals[K]: the
+    column sums over all reads (None if the call did not ask for them); end_terms[R, 2]: (A_r, T_r), the two scalars
+    behind the Begin terms every read has on all nodes at its last base, which are not row entries.  n_edges: E of the
+    model under the default keys (key e = edge e, key E + v = Begin -> v), None under a caller's map."""
+
+    def __init__(self, handle, n_reads: int, n_keys: int, totals=None, end_terms=None, n_edges: Optional[int] = None):
+        self._h = handle
+        self.n_reads, self.n_keys = int(n_reads), int(n_keys)
+        self.totals, self.end_terms = totals, end_terms
+        self.n_edges = None if n_edges is None else int(n_edges)
+        self._cache = None
+        self._by_key = None
+
+    @staticmethod
+    def from_arrays(n_keys: int, row_off, keys, usage, totals=None, end_terms=None, n_edges: Optional[int] = None) -> "ReadEdges":
+        """rows that are on the host already (a file read back, a test)"""
+        row_off = np.asarray(row_off, dtype=np.uint64)
+        u = ReadEdges(None, row_off.shape[0] - 1, n_keys, totals, end_terms, n_edges)
+        u._cache = (row_off, np.asarray(keys, dtype=np.uint32), np.asarray(usage, dtype=np.float64).reshape(-1))
+        assert int(row_off[-1]) == u._cache[1].shape[0] == u._cache[2].shape[0]
+        return u
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            from . import _ffi_edges
+            _ffi_edges.lib().phmm_read_edges_destroy(self._h)
+            self._h = None
+
+    def __len__(self) -> int:
+        return self.n_reads
+
+    def arrays(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(row_off[R + 1], keys[total], usage[total]), copied from the device on the first call"""
+        if self._cache is None:
+            from . import _ffi_edges
+            L = _ffi_edges.lib()
+            R, total = int(L.phmm_read_edges_reads(self._h)), int(L.phmm_read_edges_total(self._h))
+            row_off = np.empty(R + 1, dtype=np.uint64)
+            keys, usage = np.empty(max(total, 1), dtype=np.uint32), np.empty(max(total, 1))
+            _ffi.check(L.phmm_read_edges_export(self._h, _ptr(row_off), _ptr(keys), _ptr(usage)))
+            self._cache = (row_off, keys[:total], usage[:total])
+        return self._cache
+
+    export = arrays
+
+    def row(self, r: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(keys[n], usage[n]) of read r"""
+        row_off, keys, usage = self.arrays()
+        e0, e1 = int(row_off[r]), int(row_off[r + 1])
+        return keys[e0:e1], usage[e0:e1]
+
+    def key_freqs(self, r: int) -> np.ndarray:
+        """dense [K]: the row of read r, 0 where a key is absent"""
+        keys, usage = self.row(r)
+        out = np.zeros(self.n_keys)
+        out[keys] = usage
+        return out
+
+    def _default_keys(self) -> int:
+        if self.n_edges is None:
+            raise ValueError("the rows are keyed by a caller's map: edge_freqs / init_freqs need the default keys")
+        return self.n_edges
+
+    def edge_freqs(self, r: int) -> np.ndarray:
+        """dense [E]: the edge half of to_edge_and_init_freqs() of read r (default keys only)"""
+        return self.key_freqs(r)[:self._default_keys()]
+
+    def init_freqs(self, r: int, arrays, last_base: int) -> np.ndarray:
+        """dense [N]: the Begin half of to_edge_and_init_freqs() of read r with the end terms added (default keys only):
+        row value at key E + v + init_v (A_r + T_r e_v(last_base)); arrays: the model's PHMMArrays, last_base: the
+        read's last base as a byte value"""
+        E = self._default_keys()
+        if self.end_terms is None:
+            raise ValueError("the call did not return end terms")
+        par = arrays.param
+        init = np.exp(np.asarray(arrays.init_logp, dtype=np.float64))
+        e = np.where(np.asarray(arrays.emission) == int(last_base), math.exp(par.p_match), math.exp(par.p_mismatch))
+        a_r, t_r = float(self.end_terms[r, 0]), float(self.end_terms[r, 1])
+        return self.key_freqs(r)[E:] + init * (a_r + t_r * e)
+
+    def reads_of(self, key: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(reads[n], usage[n]): the reads whose row holds the key, in ascending order, and their entries -- the
+        transpose of row()"""
+        row_off, keys, usage = self.arrays()
+        if self._by_key is None:
+            read_of = np.repeat(np.arange(self.n_reads, dtype=np.int64), np.diff(row_off.astype(np.int64)))
+            order = np.argsort(keys, kind="stable")
+            self._by_key = (order, keys[order], read_of)
+        order, sorted_keys, read_of = self._by_key
+        e0, e1 = np.searchsorted(sorted_keys, key, side="left"), np.searchsorted(sorted_keys, key, side="right")
+        sel = order[e0:e1]
+        return read_of[sel], usage[sel]
+
+
 class PHMMModel:
     """PHMMModel<N, E> (src/hmmv2/common.rs:61-64) resident on one MI355X."""
 
@@ -774,6 +873,41 @@ class PHMMModel:
             self._h, reads._h, mappings._h, n_groups, _ptr(g_off), _ptr(g_nodes) if n_groups and g_nodes.size else None,
             _ptr(lf), _ptr(totals) if want_totals and R else None, C.byref(h)))
         return lf, ReadUsage(h, R, K, totals)
+
+    def run_with_mapping_read_edges(self, reads: ReadCollection, mappings: Mappings, edge_key=None, init_key=None,
+                                    n_keys: int = 0, want_totals: bool = True):
+        """Per read, which transitions of the graph the read crossed over its lists and how often
+        (include/phmm_amd_edges.h): PHMMOutput::to_edge_and_init_freqs() of every read, as a sparse read-by-key matrix
+        reduced on the device from the records of the list pass of run_with_mapping_edge_freqs, which never leave it
+        -> (logp_forward[R], ReadEdges).
+        n_keys = 0: the key of edge e is e and that of Begin -> v is E + v.  Otherwise edge_key[E] / init_key[N] give
+        the key (< n_keys) of every edge / Begin transition, PHMM_NO_KEY (0xffffffff) leaving a term out and None
+        leaving the whole kind out; edges on one key add (link_keys builds the map of unitig junctions).
+        want_totals: ReadEdges.totals[K], the column sums over all reads.  Every sum runs in a fixed order, so a read's
+        row depends on the model, the read, its lists and the knobs alone."""
+        from . import _ffi_edges
+        R, n_keys = len(reads), int(n_keys)
+        ek = ik = None
+        if n_keys:
+            if edge_key is not None:
+                ek = np.ascontiguousarray(edge_key, dtype=np.uint32).reshape(-1)
+                if ek.shape[0] != self.n_edges:
+                    raise ValueError("edge_key needs one entry per edge")
+            if init_key is not None:
+                ik = np.ascontiguousarray(init_key, dtype=np.uint32).reshape(-1)
+                if ik.shape[0] != self.n_nodes:
+                    raise ValueError("init_key needs one entry per node")
+        elif edge_key is not None or init_key is not None:
+            raise ValueError("edge_key / init_key need n_keys > 0")
+        K = n_keys if n_keys else self.n_edges + self.n_nodes
+        lf, end_terms = np.empty(R), np.empty((R, 2))
+        totals = np.zeros(K) if want_totals else None
+        h = C.c_void_p()
+        _ffi.check(_ffi_edges.lib().phmm_run_with_mapping_read_edges(
+            self._h, reads._h, mappings._h, n_keys, _ptr(ek) if ek is not None and ek.size else None,
+            _ptr(ik) if ik is not None else None, _ptr(lf), _ptr(end_terms) if R else None,
+            _ptr(totals) if want_totals and R else None, C.byref(h)))
+        return lf, ReadEdges(h, R, K, totals, end_terms, None if n_keys else self.n_edges)
 
     _GEN_KINDS = {"state_count": 0, "endable": 1, "emit_count": 2}
 

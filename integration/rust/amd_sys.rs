@@ -68,6 +68,10 @@ pub struct phmm_alignments {
 pub struct phmm_read_usage {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct phmm_read_edges {
+    _p: [u8; 0],
+}
 
 #[link(name = "phmm_amd")]
 /// phmm_likelihood_current_groups: a node-form move changed part of the group
@@ -224,6 +228,18 @@ extern "C" {
     pub fn phmm_read_usage_total(u: *const phmm_read_usage) -> u64;
     pub fn phmm_read_usage_export(u: *const phmm_read_usage, row_off: *mut u64, keys: *mut u32, usage: *mut f64) -> c_int;
     pub fn phmm_read_usage_destroy(u: *mut phmm_read_usage);
+
+    // (include/phmm_amd_edges.h, the tenth companion header; phmm_read_edges is an opaque handle like phmm_read_usage;
+    // PHMM_NO_KEY = 0xffff_ffff in edge_key / init_key leaves a term out)
+    pub fn phmm_run_with_mapping_read_edges(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                            n_keys: u32, edge_key: *const u32, init_key: *const u32,
+                                            out_logp_forward: *mut f64, out_end_terms: *mut f64, out_key_usage: *mut f64,
+                                            out: *mut *mut phmm_read_edges) -> c_int;
+    pub fn phmm_read_edges_reads(u: *const phmm_read_edges) -> u64;
+    pub fn phmm_read_edges_keys(u: *const phmm_read_edges) -> u64;
+    pub fn phmm_read_edges_total(u: *const phmm_read_edges) -> u64;
+    pub fn phmm_read_edges_export(u: *const phmm_read_edges, row_off: *mut u64, keys: *mut u32, usage: *mut f64) -> c_int;
+    pub fn phmm_read_edges_destroy(u: *mut phmm_read_edges);
 
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
