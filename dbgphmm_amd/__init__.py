@@ -10,7 +10,7 @@ from .graph import (PHMMArrays, SeqGraph, mock_linear, mock_crossing, toy_repeat
                     mutate_exact, tandem_repeat_polyploid_with_unique_homo_ends, genome_phmm,
                     sample_genome_reads, kp1_node_map, unitig_groups, link_keys, PHMM_NO_KEY)
 from .model import (PHMMModel, PHMMOutput, ReadCollection, Mappings, DenseTables, Likelihood, copy_num_changes,  # noqa: F401
-                    path_states, PATH_NONE, PATH_INS_BEGIN, Alignments, ListTables, ReadUsage, ReadEdges)
+                    path_states, PATH_NONE, PATH_INS_BEGIN, Alignments, ListTables, ReadUsage, ReadEdges, Pileup)
 from ._ffi import PhmmError, build  # noqa: F401
 
 from . import formats  # noqa: F401,E402  (DBG / MAP / FASTA files either side of the path)

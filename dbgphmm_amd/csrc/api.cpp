@@ -1174,6 +1174,24 @@ int phmm_read_usage_export(const phmm_read_usage *u, uint64_t *row_off, uint32_t
 
 void phmm_read_usage_destroy(phmm_read_usage *u) { delete u; }
 
+int phmm_run_with_mapping_pileup(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_lf,
+                                 double *out_node_pileup, phmm_read_usage **out) {
+    return guarded_on(m, [&] {
+        if (!m || !reads || !mp) PHMM_THROW(PHMM_EINVAL, "NULL model, reads or mappings");
+        const uint32_t N = m->N;
+        if (N > (1u << 30) - 1) PHMM_THROW(PHMM_ECAPACITY, "more than 2^30 - 1 nodes: the key 4 v + c does not fit 32 bits");
+        pileup_check_bases(reads);  // (on the host, before any device work)
+        check_mapping_nodes(m, mp, reads);
+        std::unique_ptr<phmm_read_usage> h(out ? new phmm_read_usage() : nullptr);
+        if (h) {
+            h->device = m->pool->device;
+            h->K = 4 * (uint64_t)N;
+        }
+        if (reads->R) run_with_mapping_pileup(m, reads, mp, out_lf, out_node_pileup, h.get());
+        if (out) *out = h.release();  // (a refusal has thrown: *out stays as it was)
+    });
+}
+
 int phmm_run_with_mapping_read_edges(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t n_keys,
                                      const uint32_t *edge_key, const uint32_t *init_key, double *out_lf,
                                      double *out_end_terms, double *out_key_usage, phmm_read_edges **out) {

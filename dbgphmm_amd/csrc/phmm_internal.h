@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -21,6 +22,7 @@
 #include "../../include/phmm_amd_tables.h"
 #include "../../include/phmm_amd_usage.h"
 #include "../../include/phmm_amd_edges.h"
+#include "../../include/phmm_amd_pileup.h"
 
 namespace phmm {
 
@@ -623,6 +625,33 @@ void alignments_export(const phmm_alignments *h, uint64_t *op_off, uint32_t *ops
 void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t K,
                                  const uint32_t *key_of, double *out_lf, double *out_key_usage, phmm_read_usage *h);
 void read_usage_export(const phmm_read_usage *u, uint64_t *row_off, uint32_t *keys, double *usage);
+// The keyed reduction behind the call above (read_usage.hip) with the two ends that depend on what a key is left to the
+// caller: the states pass into the workspace plane, chunks of whole reads, the stable sort, the segments, the sums into
+// the handle and the sort of the handle's keys behind the totals are the same for every key rule.
+struct KeyedUsage {
+    uint32_t K = 0;             // number of keys: a key is < K
+    uint64_t fixed_bytes = 0;   // workspace the key builder holds beside the plane and the reads' first entries
+    size_t totals_doubles = 0;  // length of the totals array
+    const char *totals_name = "";
+    // once, behind the states pass and the uploads of reads and lists: the key builder's own uploads
+    std::function<void()> setup;
+    // the sort keys of the n entries of the reads r0 .. r1-1, entry ent[r0] + i: keys[i] = (read - r0) << key_bits | key
+    // (all ones: no key), vals[i] = i; ent: device, the first entry of every read
+    std::function<void(hipStream_t s, const uint64_t *ent, uint32_t r0, uint32_t r1, uint32_t key_bits, uint32_t n,
+                       uint64_t *keys, uint32_t *vals)>
+        sort_keys;
+    // the totals from the handle's T row entries stably sorted by key (sorted_rows: their index in usage[T][3])
+    std::function<void(hipStream_t s, const uint32_t *sorted_keys, const uint32_t *sorted_rows, uint32_t T,
+                       const double *usage, double *totals)>
+        totals;
+};
+void run_with_mapping_keyed_usage(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, const KeyedUsage &ku,
+                                  double *out_lf, double *out_totals, phmm_read_usage *h);
+// per read and node, the posterior by state split by the read base there, and the per-node totals [N][9] (pileup.hip);
+// h == nullptr: scores and totals only.  pileup_check_bases: PHMM_EINVAL for a read byte other than A C G T, host only.
+void pileup_check_bases(const phmm_reads *reads);
+void run_with_mapping_pileup(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, double *out_lf,
+                             double *out_node_pileup, phmm_read_usage *h);
 // reads drawn from the model, one walk per lane (sample_reads.hip)
 void sample_reads(phmm_model *m, uint64_t first_index, uint64_t n_walks, uint32_t length, uint32_t length_kind,
                   const uint32_t *start_nodes, uint64_t n_start_nodes, uint64_t seed, uint8_t *out_bases, uint32_t *out_len,

@@ -14,6 +14,10 @@
 // Then the column totals over all reads: the handle's keys, stably sorted with their row index, one wave per key
 // (ru_col_sum).  That sort is not chunked.
 // All scratch is carved from one workspace buffer (aux[1]); what the handle owns is its own.
+//
+// The flow is run_with_mapping_keyed_usage; what a key is comes in through KeyedUsage (phmm_internal.h): the builder of the
+// sort keys in step 1 and the kernel behind the totals.  This call passes ru_sort_keys and ru_col_sum, the pileup call
+// (pileup.hip) its own two.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -55,9 +59,10 @@ uint64_t chunk_bytes(uint64_t n, size_t temp) { return 32 * n + temp + 8 * 256; 
 
 }  // namespace
 
-void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t K,
-                                 const uint32_t *key_of, double *out_lf, double *out_key_usage, phmm_read_usage *h) {
+void run_with_mapping_keyed_usage(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, const KeyedUsage &ku,
+                                  double *out_lf, double *out_key_usage, phmm_read_usage *h) {
     hipStream_t s = current_stream();
+    const uint32_t K = ku.K;
     if (m->dev.max_degree > 8) PHMM_THROW(PHMM_EINVAL, "sparse path supports node degree <= 8 (MultiDbg MAX_DEGREE is 5)");
     const uint64_t R = reads->R, n_ent = mp->total_entries, plane = sizeof(double) * 3 * n_ent;
     for (uint64_t r = 0; r < R; r++)
@@ -67,7 +72,7 @@ void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const p
     if (plane > table_budget(*m->pool))
         PHMM_THROW(PHMM_ECAPACITY, "the states plane (24 bytes per list entry) exceeds the workspace limit");
     WorkSet &ws = m->wset();
-    DevBuf &d_w = ws.aux[0], &arena = ws.aux[1], &d_ent = ws.aux[3], &d_key_of = ws.aux[7];
+    DevBuf &d_w = ws.aux[0], &arena = ws.aux[1], &d_ent = ws.aux[3];
     d_w.reserve(std::max<uint64_t>(plane, 8));
     // the posteriors by state, written in place on the device (its refusals come before any of its writes)
     std::vector<double> lf(R);
@@ -85,8 +90,7 @@ void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const p
     tm.begin();
     upload_reads(reads);
     upload_mappings(mp);
-    if (key_of) d_key_of.upload(key_of, sizeof(uint32_t) * m->N);
-    const uint32_t *dk = key_of ? d_key_of.as<uint32_t>() : nullptr;
+    if (ku.setup) ku.setup();
     const uint32_t key_bits = bits_for((uint64_t)K + 1);  // (the all-ones key is left to RU_NO_KEY)
     const uint32_t key_mask = key_bits >= 32 ? 0xffffffffu : (1u << key_bits) - 1;
 
@@ -101,7 +105,7 @@ void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const p
     st.launches[2]++;
 
     // the most entries a chunk may hold: hipcub counts in int, and the chunk's scratch fits the budget
-    const uint64_t fixed = plane + sizeof(uint64_t) * (R + 1) + (key_of ? sizeof(uint32_t) * m->N : 0);
+    const uint64_t fixed = plane + sizeof(uint64_t) * (R + 1) + ku.fixed_bytes;
     const uint64_t limit = table_budget(*m->pool), budget = limit > fixed ? limit - fixed : 0;
     uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(n_ent, 1), 1ull << 30);
     while (cap > 1 && chunk_bytes(cap, chunk_temp_bytes((uint32_t)cap, 64, s)) > budget) cap -= (cap + 3) / 4;
@@ -135,8 +139,7 @@ void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const p
             uint32_t *v0 = (uint32_t *)(ap + o_v0), *v1 = (uint32_t *)(ap + o_v1), *seg = (uint32_t *)(ap + o_seg),
                      *start = (uint32_t *)(ap + o_start);
             const dim3 grid((n + 255) / 256), block(256);
-            hipLaunchKernelGGL(ru_sort_keys, grid, block, 0, s, d_ent.as<uint64_t>(), (uint32_t)r0, (uint32_t)r1,
-                               mp->d_nodes.as<uint32_t>(), dk, key_bits, n, k0, v0);
+            ku.sort_keys(s, d_ent.as<uint64_t>(), (uint32_t)r0, (uint32_t)r1, key_bits, n, k0, v0);
             HIP_CHECK(hipGetLastError());
             size_t sb = tb;
             HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(ap + o_tmp, sb, (const uint64_t *)k0, k1, (const uint32_t *)v0, v1,
@@ -182,7 +185,7 @@ void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const p
     double *d_tot = nullptr;
     if (out_key_usage) {
         if (rows_done > (uint64_t)INT32_MAX - 1)
-            PHMM_THROW(PHMM_ECAPACITY, "out_key_usage: more than 2^31 - 2 row entries (call it on fewer reads)");
+            PHMM_THROW(PHMM_ECAPACITY, std::string(ku.totals_name) + ": more than 2^31 - 2 row entries (call it on fewer reads)");
         const uint32_t T = (uint32_t)rows_done;
         size_t tb = 0;
         if (T)
@@ -191,7 +194,7 @@ void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const p
                                                          (int)key_bits, s));
         Carver c;
         const size_t o_k1 = c.take(sizeof(uint32_t) * T), o_v0 = c.take(sizeof(uint32_t) * T),
-                     o_v1 = c.take(sizeof(uint32_t) * T), o_tot = c.take(sizeof(double) * 3 * K), o_tmp = c.take(tb);
+                     o_v1 = c.take(sizeof(uint32_t) * T), o_tot = c.take(sizeof(double) * ku.totals_doubles), o_tmp = c.take(tb);
         arena.reserve(c.top);
         char *ap = arena.as<char>();
         uint32_t *k1 = (uint32_t *)(ap + o_k1), *v0 = (uint32_t *)(ap + o_v0), *v1 = (uint32_t *)(ap + o_v1);
@@ -203,8 +206,7 @@ void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const p
                                                          (const uint32_t *)v0, v1, (int)T, 0, (int)key_bits, s));
             st.launches[2] += 2;
         }
-        hipLaunchKernelGGL(ru_col_sum, dim3((K + RU_WAVES - 1) / RU_WAVES), dim3(64 * RU_WAVES), 0, s, (const uint32_t *)k1,
-                           (const uint32_t *)v1, T, (const double *)u->d_usage.as<double>(), K, d_tot);
+        ku.totals(s, (const uint32_t *)k1, (const uint32_t *)v1, T, (const double *)u->d_usage.as<double>(), d_tot);
         HIP_CHECK(hipGetLastError());
         st.launches[2]++;
         trace("read usage totals");
@@ -212,10 +214,35 @@ void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const p
     tm.end();
     st.ms[2] += tm.total_ms();
     st.cells[2] = n_ent;
-    if (out_key_usage) copy_out(out_key_usage, d_tot, sizeof(double) * 3 * K);
+    if (out_key_usage) copy_out(out_key_usage, d_tot, sizeof(double) * ku.totals_doubles);
     put_doubles(out_lf, lf.data(), R);
     HIP_CHECK(hipStreamSynchronize(s));
     trace("read usage outputs");
+}
+
+void run_with_mapping_read_usage(phmm_model *m, const phmm_reads *reads, const phmm_mappings *mp, uint32_t K,
+                                 const uint32_t *key_of, double *out_lf, double *out_key_usage, phmm_read_usage *h) {
+    DevBuf &d_key_of = m->wset().aux[7];
+    const uint32_t N = m->N;
+    KeyedUsage ku;
+    ku.K = K;
+    ku.fixed_bytes = key_of ? sizeof(uint32_t) * N : 0;
+    ku.totals_doubles = 3 * (size_t)K;
+    ku.totals_name = "out_key_usage";
+    ku.setup = [&] {
+        if (key_of) d_key_of.upload(key_of, sizeof(uint32_t) * N);
+    };
+    ku.sort_keys = [&](hipStream_t s, const uint64_t *ent, uint32_t r0, uint32_t r1, uint32_t key_bits, uint32_t n,
+                       uint64_t *keys, uint32_t *vals) {
+        hipLaunchKernelGGL(ru_sort_keys, dim3((n + 255) / 256), dim3(256), 0, s, ent, r0, r1, mp->d_nodes.as<uint32_t>(),
+                           key_of ? d_key_of.as<uint32_t>() : nullptr, key_bits, n, keys, vals);
+    };
+    ku.totals = [&](hipStream_t s, const uint32_t *sorted_keys, const uint32_t *sorted_rows, uint32_t T, const double *usage,
+                    double *totals) {
+        hipLaunchKernelGGL(ru_col_sum, dim3((K + RU_WAVES - 1) / RU_WAVES), dim3(64 * RU_WAVES), 0, s, sorted_keys,
+                           sorted_rows, T, usage, K, totals);
+    };
+    run_with_mapping_keyed_usage(m, reads, mp, ku, out_lf, out_key_usage, h);
 }
 
 void read_usage_export(const phmm_read_usage *u, uint64_t *row_off, uint32_t *keys, double *usage) {

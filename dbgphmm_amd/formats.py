@@ -190,6 +190,46 @@ def read_alignments(path_or_file):
     return names, np.array(logp), Alignments.from_arrays(len(names), n_samples, op_off, ops, run_off, run_node, run_len)
 
 
+# ------------------------------------------------------------------------------------------------ pileup
+def write_pileup(path_or_file, pileup, emission) -> None:
+    """One tab-separated line per node of the totals of PHMMModel.run_with_mapping_pileup: node id, its emission, then
+    the nine columns -- the Match mass under read base A C G T, the Ins mass under A C G T, the Del mass -- as repr
+    floats, so that read_pileup gives back the same bits.  emission: ASCII, u8[N] or bytes."""
+    tot = np.asarray(pileup.totals, dtype=np.float64)
+    em = np.frombuffer(emission, dtype=np.uint8) if isinstance(emission, (bytes, bytearray)) else np.asarray(emission, dtype=np.uint8)
+    if tot.shape != (em.shape[0], 9):
+        raise ValueError("emission needs one base per node of the pileup")
+    fh = _open(path_or_file, "w") if isinstance(path_or_file, str) else path_or_file
+    try:
+        fh.write("# dbgphmm_amd pileup\n")
+        fh.write(f"# n_nodes={tot.shape[0]}\n")
+        fh.write("# node\temission\tmA\tmC\tmG\tmT\tiA\tiC\tiG\tiT\tdel\n")
+        for v in range(tot.shape[0]):
+            fh.write(f"{v}\t{chr(int(em[v]))}\t" + "\t".join(repr(float(x)) for x in tot[v]) + "\n")
+    finally:
+        if isinstance(path_or_file, str):
+            fh.close()
+
+
+def read_pileup(path_or_file) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (emission u8[N], totals f64[N, 9]) of a file write_pileup wrote; the lines come in node order"""
+    fh = _open(path_or_file, "r") if isinstance(path_or_file, str) else path_or_file
+    em, rows = [], []
+    try:
+        for line in fh:
+            if not line.strip() or line.startswith("#"):
+                continue
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) != 11 or int(parts[0]) != len(rows) or len(parts[1]) != 1:
+                raise ValueError("pileup lines out of order or malformed")
+            em.append(ord(parts[1]))
+            rows.append([float(x) for x in parts[2:]])
+    finally:
+        if isinstance(path_or_file, str):
+            fh.close()
+    return np.array(em, dtype=np.uint8), np.array(rows, dtype=np.float64).reshape(-1, 9)
+
+
 # ------------------------------------------------------------------------------------------------ DBG
 @dataclass
 class DbgFile:

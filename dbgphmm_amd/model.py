@@ -569,6 +569,148 @@ class ReadEdges:
         return read_of[sel], usage[sel]
 
 
+def base_codes(bases) -> np.ndarray:
+    """bytes or u8[.] of ASCII bases -> int64 codes A 0, C 1, G 2, T 3, anything else -1"""
+    b = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else np.asarray(bases, dtype=np.uint8)
+    code = np.full(256, -1, dtype=np.int64)
+    code[np.frombuffer(b"ACGT", dtype=np.uint8)] = np.arange(4)
+    return code[b]
+
+
+class Pileup:
+    """The result of PHMMModel.run_with_mapping_pileup (include/phmm_amd_pileup.h): a pileup on the graph.  The rows
+    are those of a ReadUsage under the key 4 * node + base code (A 0, C 1, G 2, T 3): per read the distinct (node, read
+    base) pairs among its list entries in ascending order and, per pair, the summed posterior of the read's Match, Ins
+    and Del states at that node at the positions showing that base.  CSR over the reads; the rows stay on the device
+    until arrays() is first called.  totals[N, 9]: per node the Match mass by read base (columns 0-3), the Ins mass by
+    read base (4-7) and the Del mass (8) over all reads; summed from the rows on the host when the call did not ask
+    for them.  The Del value of a row entry is the Del mass at the positions of that base: only its sum over the four
+    bases has a meaning of its own."""
+
+    def __init__(self, handle, n_reads: int, n_nodes: int, totals=None):
+        self._h = handle
+        self.n_reads, self.n_nodes = int(n_reads), int(n_nodes)
+        self._totals = totals
+        self._cache = None
+        self._by_key = None
+
+    @staticmethod
+    def from_arrays(n_nodes: int, row_off, keys, usage, totals=None) -> "Pileup":
+        """rows that are on the host already (a file read back, a test)"""
+        row_off = np.asarray(row_off, dtype=np.uint64)
+        u = Pileup(None, row_off.shape[0] - 1, n_nodes, None if totals is None else np.asarray(totals, dtype=np.float64))
+        u._cache = (row_off, np.asarray(keys, dtype=np.uint32), np.asarray(usage, dtype=np.float64).reshape(-1, 3))
+        assert int(row_off[-1]) == u._cache[1].shape[0] == u._cache[2].shape[0]
+        assert u._cache[1].size == 0 or int(u._cache[1].max()) < 4 * u.n_nodes
+        assert u._totals is None or u._totals.shape == (u.n_nodes, 9)
+        return u
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            from . import _ffi_usage
+            _ffi_usage.lib().phmm_read_usage_destroy(self._h)
+            self._h = None
+
+    def __len__(self) -> int:
+        return self.n_reads
+
+    def arrays(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(row_off[R + 1], keys[total], usage[total, 3]), copied from the device on the first call"""
+        if self._cache is None:
+            if not self._h:
+                raise ValueError("the call kept no rows (want_rows=False)")
+            from . import _ffi_usage
+            L = _ffi_usage.lib()
+            R, total = int(L.phmm_read_usage_reads(self._h)), int(L.phmm_read_usage_total(self._h))
+            row_off = np.empty(R + 1, dtype=np.uint64)
+            keys, usage = np.empty(max(total, 1), dtype=np.uint32), np.empty((max(total, 1), 3))
+            _ffi.check(L.phmm_read_usage_export(self._h, _ptr(row_off), _ptr(keys), _ptr(usage)))
+            self._cache = (row_off, keys[:total], usage[:total])
+        return self._cache
+
+    @property
+    def totals(self) -> np.ndarray:
+        """[N, 9]: Match by read base, Ins by read base, Del"""
+        if self._totals is None:
+            _, keys, usage = self.arrays()
+            k = keys.astype(np.int64)
+            t = np.zeros((self.n_nodes, 9))
+            np.add.at(t, (k >> 2, k & 3), usage[:, 0])
+            np.add.at(t, (k >> 2, 4 + (k & 3)), usage[:, 1])
+            np.add.at(t[:, 8], k >> 2, usage[:, 2])
+            self._totals = t
+        return self._totals
+
+    def row(self, r: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(nodes[n], base_codes[n], usage[n, 3]) of read r, ascending by (node, base code)"""
+        row_off, keys, usage = self.arrays()
+        e0, e1 = int(row_off[r]), int(row_off[r + 1])
+        return keys[e0:e1] >> 2, keys[e0:e1] & 3, usage[e0:e1]
+
+    def reads_of(self, node: int, base: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(reads[n], usage[n, 3]): the reads that list the node at a position showing the base (code 0..3), in
+        ascending order, and their entries: which reads carry which allele at the node"""
+        row_off, keys, usage = self.arrays()
+        if self._by_key is None:
+            read_of = np.repeat(np.arange(self.n_reads, dtype=np.int64), np.diff(row_off.astype(np.int64)))
+            order = np.argsort(keys, kind="stable")
+            self._by_key = (order, keys[order], read_of)
+        order, sorted_keys, read_of = self._by_key
+        key = 4 * int(node) + int(base)
+        e0, e1 = np.searchsorted(sorted_keys, key, side="left"), np.searchsorted(sorted_keys, key, side="right")
+        sel = order[e0:e1]
+        return read_of[sel], usage[sel]
+
+    @property
+    def match_counts(self) -> np.ndarray:
+        """[N, 4]: the Match mass per node and read base"""
+        return self.totals[:, 0:4]
+
+    @property
+    def ins_counts(self) -> np.ndarray:
+        """[N, 4]: the Ins mass per node and inserted base"""
+        return self.totals[:, 4:8]
+
+    @property
+    def del_counts(self) -> np.ndarray:
+        """[N]: the Del mass per node"""
+        return self.totals[:, 8]
+
+    def depth(self) -> np.ndarray:
+        """[N]: the Match mass per node, summed over the read bases"""
+        return self.match_counts.sum(axis=1)
+
+    def consensus(self) -> np.ndarray:
+        """[N] int64: the code of the heaviest Match base per node (the first of equals), -1 where the depth is 0"""
+        m = self.match_counts
+        return np.where(self.depth() > 0, np.argmax(m, axis=1), -1).astype(np.int64)
+
+    def disagreements(self, emission, min_mass: float, min_share: float = 0.5) -> np.ndarray:
+        """the nodes whose heaviest Match base is not their emission (ASCII, u8[N] or bytes), carries at least min_mass
+        and makes up at least min_share of the node's depth: where the reads agree with each other against the graph"""
+        e = base_codes(emission)
+        assert e.shape[0] == self.n_nodes
+        m, top, depth = self.match_counts, self.consensus(), self.depth()
+        mass = m[np.arange(self.n_nodes), np.maximum(top, 0)]
+        return np.nonzero((top >= 0) & (top != e) & (mass >= min_mass) & (mass >= min_share * depth))[0]
+
+    def error_profile(self, emission) -> dict:
+        """{"mismatch", "ins", "del"}: the shares of the summed Match + Ins + Del mass that are Match mass under a read
+        base other than the node's emission, Ins mass and Del mass (a node whose emission is none of A C G T adds no
+        mismatch); zeros for an empty pileup"""
+        e = base_codes(emission)
+        assert e.shape[0] == self.n_nodes
+        m = self.match_counts
+        ok = e >= 0
+        agree = float(m[ok, e[ok]].sum())
+        mismatch = float(m[ok].sum()) - agree
+        ins, dele = float(self.ins_counts.sum()), float(self.del_counts.sum())
+        total = float(m.sum()) + ins + dele
+        if total <= 0.0:
+            return {"mismatch": 0.0, "ins": 0.0, "del": 0.0}
+        return {"mismatch": mismatch / total, "ins": ins / total, "del": dele / total}
+
+
 class PHMMModel:
     """PHMMModel<N, E> (src/hmmv2/common.rs:61-64) resident on one MI355X."""
 
@@ -873,6 +1015,25 @@ class PHMMModel:
             self._h, reads._h, mappings._h, n_groups, _ptr(g_off), _ptr(g_nodes) if n_groups and g_nodes.size else None,
             _ptr(lf), _ptr(totals) if want_totals and R else None, C.byref(h)))
         return lf, ReadUsage(h, R, K, totals)
+
+    def run_with_mapping_pileup(self, reads: ReadCollection, mappings: Mappings, want_rows: bool = True,
+                                want_totals: bool = True):
+        """Per node, which bases the reads showed there, by state, over their lists (include/phmm_amd_pileup.h): the
+        values of run_with_mapping_states, which never leave the device, reduced there under the key 4 * node + base
+        code of the read base at the entry's position (A 0, C 1, G 2, T 3) -> (logp_forward[R], Pileup).
+        want_rows: the per-read rows, keyed by (node, base); want_totals: Pileup.totals[N, 9], per node the Match mass by
+        read base, the Ins mass by read base and the Del mass over all reads.  A read holding a byte other than A C G T
+        is refused.  Every sum runs in a fixed order, so a read's row depends on the model, the read and its lists
+        alone."""
+        from . import _ffi_pileup
+        R, N = len(reads), self.n_nodes
+        lf = np.empty(R)
+        totals = np.zeros((N, 9)) if want_totals else None
+        h = C.c_void_p()
+        _ffi.check(_ffi_pileup.lib().phmm_run_with_mapping_pileup(
+            self._h, reads._h, mappings._h, _ptr(lf), _ptr(totals) if want_totals and R else None,
+            C.byref(h) if want_rows else None))
+        return lf, Pileup(h if want_rows else None, R, N, totals)
 
     def run_with_mapping_read_edges(self, reads: ReadCollection, mappings: Mappings, edge_key=None, init_key=None,
                                     n_keys: int = 0, want_totals: bool = True):

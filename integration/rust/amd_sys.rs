@@ -241,6 +241,12 @@ extern "C" {
     pub fn phmm_read_edges_export(u: *const phmm_read_edges, row_off: *mut u64, keys: *mut u32, usage: *mut f64) -> c_int;
     pub fn phmm_read_edges_destroy(u: *mut phmm_read_edges);
 
+    // (include/phmm_amd_pileup.h, the eleventh companion header; the rows come back in a phmm_read_usage handle under
+    // the key 4 * node + base code, out_node_pileup is [N][9]: Match by read base, Ins by read base, Del)
+    pub fn phmm_run_with_mapping_pileup(m: *mut phmm_model, reads: *const phmm_reads, mappings: *const phmm_mappings,
+                                        out_logp_forward: *mut f64, out_node_pileup: *mut f64,
+                                        out: *mut *mut phmm_read_usage) -> c_int;
+
     pub fn phmm_last_call_stats(which: c_int, out_ms: *mut f64, out_launches: *mut u64, out_cells: *mut u64) -> c_int;
     pub fn phmm_enable_timing(on: c_int) -> c_int;
     // (include/phmm_amd_share.h, the third companion header)
